@@ -1,11 +1,19 @@
 #!/usr/bin/env python3
 """Benchmark: scheduling decisions/s (workload × cluster evaluations per second).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3] [--units TOTAL]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3] [--units TOTAL] [--dump-outputs DIR] [--full]
 
 Default: BASELINE.json's north_star configuration C3 — 1M SchedulingUnits × 1k
-FederatedClusters (C2 generator, seed 0xC3) — on one MI355X, with the C2 line
-(100k × 256) measured in the same run and embedded under ``extra``.
+FederatedClusters (C2 generator, seed 0xC3) — on one MI355X. A plain run does
+what the headline figure needs and no more: it generates and packs the batch,
+uploads it, warms up, times K steps and prints the result line. ``--full`` adds
+everything else the benchmark measures or checks, outside the timed region:
+per-stage device times and rooflines, the end-to-end timing, the CPU baseline,
+parity against the C oracle, the placement all-gather of ``--mode ranks`` and,
+in the default C3 run, the other configs (embedded under ``extra``) and the
+shard-size sweep. ``--dump-outputs DIR`` writes the placements of the last timed
+step as ``DIR/<name>.npy`` (dump_placements); the inputs are seeded, so two
+builds run with the same arguments can be compared array for array.
 
 One step = one pass of the hot path (filter → score → select [→ replicas])
 over the resident batch against the resident cluster snapshot (kad_schedule).
@@ -20,8 +28,8 @@ passes between barriers, and the step time is the max over ranks. After the
 timed region the placements are all-gathered over RCCL (fixed per-rank slot
 arrays) and timed as their own field.
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus
-``roofline`` (dominant kernel: compulsory bytes per launch ÷ its HIP-event
+Prints ONE JSON line (rank 0) with the driver's contract fields; with
+``--full`` also ``roofline`` (dominant kernel: compulsory bytes per launch ÷ its HIP-event
 time vs 8 TB/s; the PMC-measured HBM bytes and the SALU/VALU issue fractions
 from profiles/pmc_<cfg>.json when it matches the workload; SURVEY §8(d)'s
 canonical algorithmic-byte model kept only for transparency),
@@ -310,8 +318,51 @@ def verify_rows(snap, batch, fwk, res, want=None, n_want=0, max_units=200_000):
             "oracle": "oracle/kad_ref.c", "windows": len(wins)}
 
 
+DUMP_MAX_BYTES = 60_000_000  # of the 64 MB a dump may take: headroom for the .npy headers
+DUMP_SEED = 0xD0
+
+
+def _save(d, name, a, dtype):
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a, dtype))
+
+
+def dump_placements(d, res):
+    """--dump-outputs: what a caller of the timed path receives (kad_results_download after the last timed
+    step) as DIR/<name>.npy. Per dumped unit: ``unit`` (its index in the batch), ``status``, ``count``,
+    ``flags`` and ``placement_offset`` (n + 1 prefix sums of count); per placement, in unit order:
+    ``placement_cluster`` and ``placement_replicas`` — the written slots [out_off[w], out_off[w] + count[w])
+    of each unit only (the rest of a unit's slot range is never written). float32 where every value is an
+    integer below 2^24 (status, count, cluster ids), float64 elsewhere (exact below 2^53).
+    A batch whose arrays would pass DUMP_MAX_BYTES is sampled by unit: a permutation seeded with DUMP_SEED,
+    cut where the units' sizes — 32 B each plus 12 B per slot of their range, which the batch fixes, not the
+    result — reach the budget, so that two builds dump the same units."""
+    W = len(res.status)
+    off = np.asarray(res.out_off[:W + 1], np.int64)
+    bound = np.diff(off)
+    cost = 32 + 12 * bound
+    if int(cost.sum()) <= DUMP_MAX_BYTES:
+        units = np.arange(W, dtype=np.int64)
+    else:
+        perm = np.random.default_rng(DUMP_SEED).permutation(W)
+        units = np.sort(perm[:int(np.searchsorted(np.cumsum(cost[perm]), DUMP_MAX_BYTES, side="right"))])
+    cnt = np.clip(res.count[units].astype(np.int64), 0, bound[units])
+    poff = np.zeros(len(units) + 1, np.int64)
+    np.cumsum(cnt, out=poff[1:])
+    idx = np.repeat(off[units], cnt) + (np.arange(int(poff[-1])) - np.repeat(poff[:-1], cnt))
+    _save(d, "unit", units, np.float64)
+    _save(d, "status", res.status[units], np.float32)
+    _save(d, "count", res.count[units], np.float32)
+    _save(d, "flags", res.flags[units], np.float64)
+    _save(d, "placement_offset", poff, np.float64)
+    _save(d, "placement_cluster", res.cluster[idx], np.float32)
+    _save(d, "placement_replicas", res.replicas[idx], np.float64)
+
+
 # ------------------------------------------------------------------------ scheduling bench
-def bench_schedule(args, cfg, rank, world, local, dist, W_total=None, cpu_seconds=None):
+def bench_schedule(args, cfg, rank, world, local, dist, W_total=None, cpu_seconds=None, dump=None):
+    """One scheduling config: set-up, warm-up, the timed steps, rank 0's placements to ``dump`` when given.
+    A plain run returns the headline line there; everything after that is --full's."""
     import torch  # noqa: F401  (HIP runtime initialised by torch before libkad.so)
 
     from kubeadmiral_amd import columns as CO
@@ -399,11 +450,21 @@ def bench_schedule(args, cfg, rank, world, local, dist, W_total=None, cpu_second
     if dist is not None:
         dist.barrier()
     elapsed = time.perf_counter() - t0
-    res = ctx.download()
+    res = ctx.download() if args.full or (dump and rank == 0) else None  # the last timed step's placements
     paths = ctx.path_counts()
     sp = ctx.snapshot_paths()  # the main kernel and the snapshot's resource class (per-cluster clean)
     paths["main"] = "wide" if sp["wide"] else "lean"
     paths["resource_class"] = sp["resource_class"]
+    if dump and rank == 0:
+        dump_placements(dump, res)
+    if not args.full:
+        ms = elapsed / max(1, args.steps) * 1e3
+        if dist is not None:
+            t = torch.tensor([ms], dtype=torch.float64, device=cdev)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            ms = float(t[0])
+        ctx.close()
+        return headline(args, cfg, world, W_total, C, batch.W, ms, paths) if rank == 0 else None
     # per-stage device time (HIP events on the context's stream), outside the timed region
     ctx.set_timing(True)
     st = []
@@ -508,6 +569,17 @@ def bench_group(args, cfg, devices, dist, rank):
     sp = g.member(0).snapshot_paths()
     paths["main"] = "wide" if sp["wide"] else "lean"
     paths["resource_class"] = sp["resource_class"]
+    if args.dump_outputs:
+        dump_placements(args.dump_outputs, res)
+    if not args.full:
+        ulo, _ = g.ranges()
+        out = headline(args, cfg, N, W_total, C, int(np.max(np.diff(ulo))), ms, paths)
+        out["config"]["parallelism"] = f"dp{N} (kad_group: one process, {N} devices)"
+        out["config"]["rccl_world_size"] = None
+        out["group"] = {"devices": list(devices), "member_total_ms": None, "upload_ms": upload_ms,
+                        "download_ms": d2h_ms, "mode": "group"}
+        g.close()
+        return out
     # per-member stage times (timing on, outside the timed region): the slowest member per stage
     g.set_timing(True)
     per = []
@@ -622,6 +694,15 @@ def schedule_line(args, cfg, world, W_total, C, batch, snap, fwk, res, stage, ms
                        {"salu_frac": (v["issue"] or {}).get("salu_frac"), "valu_frac": (v["issue"] or {}).get("valu_frac"),
                         "hbm_measured_frac": v["hbm"]["measured_frac"], "hbm_compulsory_frac": v["hbm"]["compulsory_frac"]}
                        for k, v in kernels.items()}
+    out = headline(args, cfg, world, W_total, C, W0r, ms, paths)
+    out["config"]["stage_ms"] = stage
+    out["roofline"] = roof
+    return out
+
+
+def headline(args, cfg, world, W_total, C, units_per_gpu, ms, paths):
+    """The result line of one scheduling config as a plain run prints it: the timed steps' figure and the
+    workload. --full fills in the rest (schedule_line and its callers)."""
     return {
         "metric": "scheduling decisions/sec (workload x cluster evals/s)",
         "value": W_total * C / (ms * 1e-3),
@@ -635,10 +716,9 @@ def schedule_line(args, cfg, world, W_total, C, batch, snap, fwk, res, stage, ms
         "vs_baseline": None,
         "dtype": "int64",
         "data": "synthetic (seeded SURVEY.md §8(d) generator; no cluster/dataset available)",
-        "config": {"workload": f"{cfg}: {WORKLOAD_DESC[cfg]}", "units_total": W_total, "units_per_gpu": W0r,
-                   "clusters": C, "parallelism": f"dp{world}", "rccl_world_size": world,
-                   "stage_ms": stage, "paths": paths},
-        "roofline": roof,
+        "config": {"workload": f"{cfg}: {WORKLOAD_DESC[cfg]}", "units_total": W_total, "units_per_gpu": units_per_gpu,
+                   "clusters": C, "parallelism": f"dp{world}", "rccl_world_size": world, "paths": paths},
+        "roofline": None,
         "allgather": None,
         "end_to_end": None,
         "cpu_baseline": None,
@@ -734,9 +814,11 @@ def write_full(out: dict, cfg: str):
         return None
 
 
-def emit(out: dict, cfg: str):
-    """Rank 0's stdout: one compact line per extra config, then the headline line LAST (≤ HEADLINE_MAX)."""
-    out["detail"] = write_full(out, cfg)
+def emit(out: dict, cfg: str, full: bool = True):
+    """Rank 0's stdout: one compact line per extra config, then the headline line LAST (≤ HEADLINE_MAX).
+    ``full``: the uncompacted result also goes to a file (write_full), named under ``detail``."""
+    if full:
+        out["detail"] = write_full(out, cfg)
     lines = []
     for k, v in (out.get("extra") or {}).items():
         c = compact_line(v, headline=False)
@@ -1011,12 +1093,21 @@ def bench_trigger(args, cfg, rank, world, local, dist):
     if dist is not None:
         dist.barrier()
     ms = (time.perf_counter() - t0) / max(1, args.steps) * 1e3
-    tot, summ = [], []
-    for _ in range(max(3, min(args.steps, 10))):
-        ctx.trigger_run()
-        a, b = ctx.trigger_timing()
-        tot.append(a)
-        summ.append(b)
+    if args.dump_outputs and rank == 0:  # one u32 hash per object (exact in float64)
+        h = ctx.trigger_download()
+        if 16 * len(h) > DUMP_MAX_BYTES:  # a seeded sample of the objects, and which they are
+            pick = np.sort(np.random.default_rng(DUMP_SEED).permutation(len(h))[:DUMP_MAX_BYTES // 16])
+            _save(args.dump_outputs, "object", pick, np.float64)
+            h = h[pick]
+        _save(args.dump_outputs, "trigger_hash", h, np.float64)
+    tot, summ = [0.0], [0.0]
+    if args.full:  # the two kernels' device times (HIP events), in passes of their own
+        tot, summ = [], []
+        for _ in range(max(3, min(args.steps, 10))):
+            ctx.trigger_run()
+            a, b = ctx.trigger_timing()
+            tot.append(a)
+            summ.append(b)
     tot_ms, sum_ms = float(np.mean(tot)), float(np.mean(summ))
     units_total = W * world
     if dist is not None:
@@ -1036,15 +1127,18 @@ def bench_trigger(args, cfg, rank, world, local, dist):
             "data": "synthetic (seeded federated Deployments, policies and joined clusters)",
             "config": {"workload": f"{cfg}: {WORKLOAD_DESC[cfg]}", "objects_per_gpu": W, "objects_total": units_total,
                        "clusters": C, "cluster_part_bytes": len(suffix), "object_part_bytes_avg": pre_bytes / max(1, W),
-                       "parallelism": f"dp{world}",
-                       "kernel_ms": {"cluster_part_summary": sum_ms, "objects": tot_ms - sum_ms}},
-            "roofline": {"bound": "valu", "achieved": steps / (sum_ms * 1e-3), "peak": FNV_STEP_PEAK,
-                         "unit": "FNV steps/s", "frac": steps / (sum_ms * 1e-3) / FNV_STEP_PEAK, "traffic": None,
-                         "kernel": "trig_segment_kernel + trig_compose_kernel (256 residue chains over the cluster part)",
-                         "objects_kernel_gbs": obj_bytes / max(1e-9, (tot_ms - sum_ms) * 1e-3) / 1e9},
+                       "parallelism": f"dp{world}"},
+            "roofline": None,
             "cpu_baseline": None,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            out["config"]["kernel_ms"] = {"cluster_part_summary": sum_ms, "objects": tot_ms - sum_ms}
+            out["roofline"] = {
+                "bound": "valu", "achieved": steps / (sum_ms * 1e-3), "peak": FNV_STEP_PEAK,
+                "unit": "FNV steps/s", "frac": steps / (sum_ms * 1e-3) / FNV_STEP_PEAK, "traffic": None,
+                "kernel": "trig_segment_kernel + trig_compose_kernel (256 residue chains over the cluster part)",
+                "objects_kernel_gbs": obj_bytes / max(1e-9, (tot_ms - sum_ms) * 1e-3) / 1e9}
+        if args.full and world == 1 and not args.no_cpu_baseline:
             from oracle import ref
 
             threads, n_machine, quota = host_cpus()
@@ -1072,12 +1166,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="c3", choices=sorted(WORKLOAD_DESC))
     ap.add_argument("--units", type=int, default=None, help="total units (default: the config's W)")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the embedded C2/C4/C5 lines of the default run")
-    ap.add_argument("--extras", default="c3r,c3p,c2,c4,c5", help="configs embedded under `extra` in the default C3 run")
-    ap.add_argument("--no-sweep", action="store_true", help="skip the C3 shard-size sweep of the default run")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the pack -> upload -> schedule -> download timing")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: per-stage times and "
+                         "rooflines, end-to-end timing, CPU baseline, parity against the C oracle, the placement "
+                         "all-gather (--mode ranks), and in the default C3 run the other configs and the shard sweep")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the placements of the last timed step as DIR/<name>.npy (dump_placements)")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="(--full) time budget of the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="(--full) skip the embedded C2/C4/C5 lines of the default run")
+    ap.add_argument("--extras", default="c3r,c3p,c2,c4,c5", help="(--full) configs embedded under `extra` in the default C3 run")
+    ap.add_argument("--no-sweep", action="store_true", help="(--full) skip the C3 shard-size sweep of the default run")
+    ap.add_argument("--no-e2e", action="store_true", help="(--full) skip the pack -> upload -> schedule -> download timing")
     ap.add_argument("--backend", default="nccl", choices=("nccl", "gloo"),
                     help="gloo: rehearse the multi-rank path with host-tensor transfers (e.g. ranks sharing one GPU)")
     ap.add_argument("--share-gpu", action="store_true", help="every rank uses device 0 (rehearsal on a 1-GPU box)")
@@ -1122,9 +1222,9 @@ def main():
     if cfg.startswith("t"):
         out = bench_trigger(args, cfg, rank, world, local, dist)
     else:
-        out = bench_schedule(args, cfg, rank, world, local, dist)
-        default_run = cfg == "c3" and world == 1 and args.units is None
-        # the default run also measures every other single-GPU config (C2 100k x 256, C4 1M x 512 Divide,
+        out = bench_schedule(args, cfg, rank, world, local, dist, dump=args.dump_outputs)
+        default_run = args.full and cfg == "c3" and world == 1 and args.units is None
+        # the default run with --full also measures every other single-GPU config (C2 100k x 256, C4 1M x 512 Divide,
         # C5 100k x 10k) on the same box and embeds their full lines, sampled CPU baselines included
         if default_run and not args.no_extra:
             out["extra"] = {}
@@ -1135,7 +1235,7 @@ def main():
         if default_run and not args.no_sweep:
             out["shard_sweep"] = shard_sweep(args, cfg, local, out["ms_per_step"])
     if rank == 0 and out is not None:
-        emit(out, cfg)
+        emit(out, cfg, args.full)
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
@@ -1166,7 +1266,7 @@ def main_group(args) -> int:
         dist.barrier()
     out = bench_group(args, args.config, devices, dist, rank)
     if rank == 0 and out is not None:
-        emit(out, args.config)
+        emit(out, args.config, args.full)
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()

@@ -14,7 +14,7 @@ lib, cfg = sys.argv[1], sys.argv[2]
 from kubeadmiral_amd import runtime
 if lib == "old":
     runtime.LIB_PATH = os.path.join(os.path.dirname(os.path.dirname(runtime.__file__)), "ablibs", "libkad_old.so")
-sys.argv = ["bench.py", "--config", cfg, "--steps", "20", "--warmup", "3", "--no-cpu-baseline", "--no-extra",
+sys.argv = ["bench.py", "--config", cfg, "--steps", "20", "--warmup", "3", "--full", "--no-cpu-baseline", "--no-extra",
             "--no-sweep", "--no-e2e"]
 runpy.run_path("bench.py", run_name="__main__")
 PY

@@ -4,21 +4,22 @@
 # checks src_hash), then the driver's default bench line and a kernel trace of it.
 #   scripts/final_bench.sh TAG "c4 c5"
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
-mkdir -p gpurun_out
+out=${KAD_OUT_DIR:-bench_out}  # logs and result lines (scripts/profile.sh writes there too)
+mkdir -p "$out"
 export TMPDIR=/tmp
 tag=${1:-fin}; cfgs=${2:-}
 for cfg in $cfgs; do
-  timeout -k 10 1000 bash scripts/profile.sh "$cfg" "$tag" > "gpurun_out/${tag}_prof_$cfg.log" 2>&1
-  rc=$?; echo "== prof $cfg rc=$rc"; tail -n 3 "gpurun_out/${tag}_prof_$cfg.log"
+  timeout -k 10 1000 bash scripts/profile.sh "$cfg" "$tag" > "$out/${tag}_prof_$cfg.log" 2>&1
+  rc=$?; echo "== prof $cfg rc=$rc"; tail -n 3 "$out/${tag}_prof_$cfg.log"
   [ $rc -ne 0 ] && exit $rc
-  cp "gpurun_out/prof_${cfg}_${tag}/pmc_$cfg.json" "profiles/pmc_$cfg.json" || exit 1
+  cp "$out/prof_${cfg}_${tag}/pmc_$cfg.json" "profiles/pmc_$cfg.json" || exit 1
 done
-timeout -k 10 900 python bench.py --steps 20 --warmup 3 > "gpurun_out/${tag}_bench.json" 2> "gpurun_out/${tag}_bench.log"
-rc=$?; echo "== bench rc=$rc"; tail -n 3 "gpurun_out/${tag}_bench.log"
+timeout -k 10 900 python bench.py --full --steps 20 --warmup 3 > "$out/${tag}_bench.json" 2> "$out/${tag}_bench.log"
+rc=$?; echo "== bench rc=$rc"; tail -n 3 "$out/${tag}_bench.log"
 [ $rc -ne 0 ] && exit $rc
-python - "$tag" <<'PY'
+python - "$out/${tag}_bench.json" <<'PY'
 import json, sys
-d = json.loads(open(f"gpurun_out/{sys.argv[1]}_bench.json").read().strip().splitlines()[-1])
+d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 def show(d, n):
     r = d.get("roofline") or {}
     print(n, "%.4g" % d["value"], round(d["ms_per_step"], 4), r.get("bound"), r.get("frac"), r.get("pmc"),

@@ -17,7 +17,7 @@ for cfg in $phases; do
     > gpurun_out/${tag}_phase_$cfg.log 2>&1 || { echo "phase $cfg failed"; tail -20 gpurun_out/${tag}_phase_$cfg.log; exit 1; }
 done
 for cfg in $benches; do
-  timeout -k 10 300 python bench.py --config $cfg --steps 20 --warmup 3 --no-cpu-baseline --no-extra --no-sweep \
+  timeout -k 10 300 python bench.py --config $cfg --steps 20 --warmup 3 --full --no-cpu-baseline --no-extra --no-sweep \
     > gpurun_out/${tag}_bench_$cfg.json 2> gpurun_out/${tag}_bench_$cfg.log || { echo "bench $cfg failed"; tail -20 gpurun_out/${tag}_bench_$cfg.log; exit 1; }
   python - "$tag" "$cfg" <<'PY'
 import json, sys

@@ -20,7 +20,7 @@ if [ -n "$punits" ]; then
 fi
 for cu in $benches; do
   cfg=${cu%%:*}; u=""; [ "$cu" != "$cfg" ] && u="--units ${cu#*:}"
-  timeout -k 10 300 python bench.py --config $cfg $u --steps 20 --warmup 3 --no-cpu-baseline --no-extra --no-sweep --no-e2e \
+  timeout -k 10 300 python bench.py --config $cfg $u --steps 20 --warmup 3 --full --no-cpu-baseline --no-extra --no-sweep --no-e2e \
     > gpurun_out/${tag}_bench_$cfg${cu#$cfg}.json 2> gpurun_out/${tag}_bench.log || { echo "bench $cu failed"; tail -20 gpurun_out/${tag}_bench.log; exit 1; }
   python - "gpurun_out/${tag}_bench_$cfg${cu#$cfg}.json" "$cu" <<'PY'
 import json, sys

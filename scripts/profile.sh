@@ -4,7 +4,7 @@
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
 cfg=${1:-c2}; tag=${2:-run}
-out=gpurun_out/prof_${cfg}_${tag}
+out=${KAD_OUT_DIR:-bench_out}/prof_${cfg}_${tag}
 mkdir -p "$out"
 B="python bench.py --config $cfg --steps 5 --warmup 1 --no-cpu-baseline --no-extra --no-sweep --no-e2e ${UNITS:+--units $UNITS}"
 run() {  # name, rocprof args...

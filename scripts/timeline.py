@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-step timeline of a rocprofv3 kernel trace: kernel durations, their overlap and the idle gaps between them.
 
-    rocprofv3 --kernel-trace --output-format csv -d OUT -o run -- python bench.py --config c3 --units 125000 ...
+    rocprofv3 --kernel-trace --output-format csv -d OUT -o run -- python bench.py --config c3 --units 125000 --full ...
     python scripts/timeline.py OUT [--last N] [--json out.json]
 
 The trace's dispatches are grouped into steps (a step starts at each req_row_kernel / req_mask_kernel /

@@ -16,7 +16,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_two_ranks_share_one_gpu():
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--mode", "ranks", "--share-gpu", "--backend", "gloo",
-           "--config", "c2", "--units", "20000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extra"]
+           "--config", "c2", "--units", "20000", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline",
+           "--no-extra"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=280)
     r0 = "\n".join(ln for ln in p.stderr.splitlines() if ln.startswith("[rank0]"))
@@ -32,7 +33,7 @@ def test_bench_two_ranks_share_one_gpu():
 
 def _group_line(extra_env=None, launcher=False):
     args = ["--gpus", "4", "--group-devices", "0,0,0,0", "--config", "c3", "--units", "200000", "--steps", "3",
-            "--warmup", "1"]
+            "--warmup", "1", "--full"]
     if launcher:  # the driver's SCALE launch: one rank per GPU, rank 0 drives the group
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=4",
                "--master-addr=127.0.0.1", "--master-port=29517", os.path.join(ROOT, "bench.py")] + args
