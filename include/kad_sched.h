@@ -441,6 +441,35 @@ int kad_plan_rows(kad_ctx* ctx, int n_rows, const int32_t* row_off, const uint32
  * kad_schedule (feasible: u8[W*C]; total: i64[W*C], meaningful where feasible). */
 int kad_debug_scores(kad_ctx* ctx, const kad_profile* profile, uint8_t* feasible, int64_t* total);
 
+/* ------------------------------------------------------ filter diagnosis
+ * Why a unit got no cluster. findClustersThatFitWorkload logs, per cluster, the reason of the filter
+ * plugin that rejected it (core/generic_scheduler.go:161-166); that plugin is the first one in the
+ * framework's filter order whose Filter does not succeed (RunFilterPlugins,
+ * framework/runtime/framework.go:114-126). kad_profile keeps the filters as a mask, so the order is an
+ * argument here: filter_order lists the KAD_PL_* ids of the filter plugins in framework order
+ * (EnabledPlugins.FilterPlugins) and must be a permutation of the bits of profile->filter_mask.
+ * For each listed unit of the resident batch (unit_idx entries in [0, W), any order, repeats allowed; row i
+ * of every output belongs to unit_idx[i]) the call reports how many clusters each plugin rejected, how many
+ * passed every filter, which resources ClusterResourcesFit found short (fitsRequest collects all of them,
+ * clusterresources/fit.go:73-134, so the three counts may overlap) and, optionally, the rejecting plugin
+ * per cluster. Sticky units are not filtered (generic_scheduler.go:101-104): zero counts, feasible = -1.
+ * The profile must be the one the batch was packed for, as for kad_schedule. Works before or after
+ * kad_schedule on the resident snapshot and batch (it rebuilds the requirement rows itself) and leaves the
+ * last results, the timings and any later kad_schedule as they were. Runs on the ctx stream; blocks until
+ * the outputs are in the caller's buffers. Typical use: after a schedule, over the KAD_ST_NO_FEASIBLE
+ * units only. Members of a kad_group: through kad_group_member (unit indices within the member's shard). */
+typedef struct kad_explain_view {
+  int32_t* rejected;    /* [n][5]  by KAD_PL_* id 0..4: clusters whose first failing filter is that plugin */
+  int32_t* feasible;    /* [n]     clusters passing every enabled filter; -1 = sticky unit, not filtered */
+  int32_t* fit_detail;  /* [n][3]  cpu, memory, any scalar — among rejected[.][FIT]; may be NULL */
+  uint8_t* first_fail;  /* [n][C]  plugin id or 0xFF (passed, or a sticky unit); may be NULL */
+} kad_explain_view;
+int kad_explain(kad_ctx* ctx, const kad_profile* profile, const int32_t* filter_order, int n_order,
+                const int32_t* unit_idx, int n_units, const kad_explain_view* out);
+/* Device time of the last kad_explain that launched (n_units > 0), from HIP events on the ctx stream:
+ * ms[0] = the requirement rows' rebuild, ms[1] = filter_explain_kernel. No reference counterpart. */
+int kad_explain_timing(kad_ctx* ctx, float ms[2]);
+
 /* ------------------------------------------------ result application (§8 f3)
  * applySchedulingResult (pkg/controllers/scheduler/scheduler.go:632-695) writes a unit's result into its
  * federated object: the scheduler controller's placement (util.SetPlacementClusterNames,

@@ -29,6 +29,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 from . import framework as F
 from . import objects as O
 from . import types as T
+from .pack import ST_NO_FEASIBLE
 from .runtime import BatchScheduler, Context, TriggerHasher
 
 STATUS_ALL_OK = "AllOK"   # worker.StatusAllOK
@@ -43,6 +44,7 @@ class ReconcileOutcome:
     modified: bool = False                       # applySchedulingResult changed the object
     result: Optional[T.ScheduleResult] = None
     error: str = ""
+    diagnosis: str = ""                          # reconcile(explain=True): why no cluster was feasible
 
 
 class BatchReconciler:
@@ -64,8 +66,8 @@ class BatchReconciler:
         return F.Framework(F.apply_profile(F.default_enabled_plugins(), profile))
 
     def reconcile(self, objs: Sequence[dict], policies: Dict[Tuple[str, str], O.PropagationPolicy],
-                  clusters: List[T.FederatedCluster], profiles: Optional[Dict[str, Optional[dict]]] = None
-                  ) -> List[ReconcileOutcome]:
+                  clusters: List[T.FederatedCluster], profiles: Optional[Dict[str, Optional[dict]]] = None,
+                  explain: bool = False) -> List[ReconcileOutcome]:
         """Reconcile every object against the joined ``clusters``.
 
         ``policies`` maps (namespace, name) → policy ("" namespace for
@@ -74,10 +76,13 @@ class BatchReconciler:
         ``ReconcileOutcome.stage``: ``policy-not-found``, ``profile-not-found``,
         ``trigger-error``, ``unchanged`` (trigger hash equal), ``no-scheduling``,
         ``unit-error``, ``framework-error``, ``schedule-error``, ``apply-error``,
-        ``scheduled``.
+        ``scheduled``. ``explain``: every object scheduled with no feasible cluster gets
+        ``ReconcileOutcome.diagnosis``, the per-plugin rejection counts of its unit
+        (``FilterDiagnosis.message``), from one kad_explain per framework batch over just those units.
         """
         profiles = profiles or {}
         out: List[Optional[ReconcileOutcome]] = [None] * len(objs)
+        why: Dict[int, str] = {}
         ctx_pol: List[Optional[O.PropagationPolicy]] = [None] * len(objs)
         ctx_prof: List[Optional[str]] = [None] * len(objs)
 
@@ -125,7 +130,8 @@ class BatchReconciler:
                 to_schedule.append(i)
 
         if self.native_objects:
-            self._schedule_and_apply_native(objs, to_schedule, ctx_pol, ctx_prof, profiles, clusters, out)
+            self._schedule_and_apply_native(objs, to_schedule, ctx_pol, ctx_prof, profiles, clusters, out,
+                                            why if explain else None)
             return out  # type: ignore[return-value]
 
         # schedule :445-521 — units grouped by framework, one GPU batch per framework
@@ -149,6 +155,9 @@ class BatchReconciler:
                     out[i] = ReconcileOutcome(STATUS_ERROR, "framework-error", error=str(e))
                 continue
             res = self.scheduler.schedule(fwk, [su for _, su in members], clusters)
+            if explain:  # ScheduleResult(None) is the NO_FEASIBLE unit's result (results.to_schedule_result)
+                self._explain(fwk, [(i, w) for w, ((i, _), r) in enumerate(zip(members, res))
+                                    if isinstance(r, T.ScheduleResult) and r.suggested_clusters is None], why)
             for (i, _), r in zip(members, res):
                 if isinstance(r, T.ScheduleError):
                     out[i] = ReconcileOutcome(STATUS_ERROR, "schedule-error", error=str(r))
@@ -172,8 +181,16 @@ class BatchReconciler:
             except (O.ObjectError, O.GoPanic) as e:
                 out[i] = ReconcileOutcome(STATUS_ERROR, "apply-error", result=r, error=str(e))
                 continue
-            out[i] = ReconcileOutcome(STATUS_ALL_OK, "scheduled", True, modified, r)
+            out[i] = ReconcileOutcome(STATUS_ALL_OK, "scheduled", True, modified, r, diagnosis=why.get(i, ""))
         return out  # type: ignore[return-value]
+
+    def _explain(self, fwk: F.Framework, pairs: List[Tuple[int, int]], why: Dict[int, str]) -> None:
+        """``why[i]`` = the filter diagnosis of unit w of the batch just scheduled, for (object i, unit w) pairs."""
+        if not pairs:
+            return
+        d = self.ctx.explain(fwk, [w for _, w in pairs])
+        for k, (i, _) in enumerate(pairs):
+            why[i] = d.message(k)
 
     # ------------------------------------------------------------------ the native object path
     @staticmethod
@@ -189,7 +206,7 @@ class BatchReconciler:
             threshold = O.parse_duration(am.when.pod_unschedulable_for)
         return not pol.spec.disable_follower_scheduling, threshold
 
-    def _schedule_and_apply_native(self, objs, to_schedule, ctx_pol, ctx_prof, profiles, clusters, out):
+    def _schedule_and_apply_native(self, objs, to_schedule, ctx_pol, ctx_prof, profiles, clusters, out, why=None):
         """The schedule and apply stages over the objects' JSON: per framework one kad_units_from_objects, one
         packed GPU batch, then one kad_apply_results for every object with a result."""
         import json
@@ -231,6 +248,8 @@ class BatchReconciler:
                 continue
             res, snap = self.scheduler.schedule_columns(fwk, built.cols, clusters)
             names = snap.names
+            if why is not None:
+                self._explain(fwk, [(i, w) for i, w in ok if int(res.status[w]) == ST_NO_FEASIBLE], why)
             for i, w in ok:
                 r = to_schedule_result_cols(res, w, built.cols, names)
                 if isinstance(r, T.ScheduleError):
@@ -273,7 +292,8 @@ class BatchReconciler:
                 for (a, b), v in zip(K.APPLY_FIELDS, fields[k]):
                     if v is not None:
                         objs[i].setdefault(a, {})[b] = json.loads(v)
-            out[i] = ReconcileOutcome(STATUS_ALL_OK, "scheduled", True, bool(modified[k]), r)
+            out[i] = ReconcileOutcome(STATUS_ALL_OK, "scheduled", True, bool(modified[k]), r,
+                                      diagnosis=(why or {}).get(i, ""))
 
     # ------------------------------------------------------------------ the reconcile over JSON texts
     def reconcile_texts(self, texts: Sequence, policies: Sequence, clusters: List[T.FederatedCluster],

@@ -83,6 +83,10 @@ struct kad_ctx {
   int plan_force_ws = 0;  // kad_debug_plan_force_workspace: kad_plan_rows through the workspace planner (tests)
   void* d_diff = nullptr;  // kad_result_diff: canonical object state + flags
   size_t diff_cap = 0;
+  void* d_explain = nullptr;  // kad_explain: unit list, then the outputs
+  size_t explain_cap = 0;
+  hipEvent_t xev[3] = {nullptr, nullptr, nullptr};  // kad_explain: start, after the requirement rows, end
+  bool explained = false;     // xev hold a kad_explain run
   // HIP event records around the stages (kad_set_timing); timed = the last
   // kad_schedule recorded them
   bool timing = false, timed = false;
@@ -440,6 +444,11 @@ int kad_ctx_create(int hip_device, kad_ctx** out) {
       kad_ctx_destroy(c);
       return KAD_EHIP;
     }
+  for (auto& e : c->xev)
+    if (hipEventCreate(&e) != hipSuccess) {
+      kad_ctx_destroy(c);
+      return KAD_EHIP;
+    }
   *out = c;
   return KAD_OK;
 }
@@ -451,11 +460,13 @@ int kad_ctx_destroy(kad_ctx* c) {
   if (c->side) (void)hipStreamSynchronize(c->side);  // the row kernel may run there: drain it before any free
   for (void* p : {c->d_snap, c->d_batch, (void*)c->d_plan_rows, c->d_plan_hdr, c->d_plan_big, (void*)c->d_req_mask, (void*)c->d_status, (void*)c->d_count,
                   (void*)c->d_cluster, (void*)c->d_flags, (void*)c->d_replicas, c->d_scratch, c->d_rec, c->d_delta, c->d_sw, c->d_cw, c->d_defer, c->d_wq, c->d_slices, c->d_fit, c->d_reqseg, c->d_rowslab, c->d_vrows, c->d_rescols,
-                  c->t_suffix, c->t_prefix, c->t_work, c->t_tabs, c->d_diff})
+                  c->t_suffix, c->t_prefix, c->t_work, c->t_tabs, c->d_diff, c->d_explain})
     if (p) (void)hipFree(p);
   for (auto& e : c->ev)
     if (e) (void)hipEventDestroy(e);
   for (auto& e : c->tev)
+    if (e) (void)hipEventDestroy(e);
+  for (auto& e : c->xev)
     if (e) (void)hipEventDestroy(e);
   if (c->side) {
     (void)hipStreamSynchronize(c->side);
@@ -1631,6 +1642,78 @@ int kad_debug_scores(kad_ctx* c, const kad_profile* p, uint8_t* feasible, int64_
   });
 }
 
+// The filter diagnosis of the listed units (kad_explain.hip). Reads the resident snapshot and batch and the
+// requirement rows (rebuilt here by the launch schedule_locked uses: ~10 us at the bench sizes, and no
+// currency flag to keep through every upload and update path); writes only its own buffer.
+int kad_explain(kad_ctx* c, const kad_profile* p, const int32_t* order, int n_order, const int32_t* unit_idx,
+                int n_units, const kad_explain_view* out) {
+  return guarded(c, [&]() -> int {
+    if (!c) return KAD_EINVAL;
+    std::lock_guard<std::mutex> g(c->mu);
+    if (!c->have_snapshot || !c->have_batch) return fail(c, KAD_ESTATE, "snapshot and batch must be uploaded first");
+    if (int r = validate_profile(c, p)) return r;
+    if (p->filter_mask != c->batch_hdr.packed_filter_mask)
+      return fail(c, KAD_EINVAL, "profile differs from the one the batch was packed for");
+    if (n_order < 0 || n_order > 5 || (n_order && !order)) return fail(c, KAD_EINVAL, "filter order: 0..5 plugin ids");
+    uint32_t seen = 0, packed = 0;
+    for (int k = 0; k < n_order; k++) {
+      if (order[k] < 0 || order[k] > KAD_PL_CLUSTER_AFFINITY || (seen >> order[k] & 1))
+        return fail(c, KAD_EINVAL, "filter order: not a filter plugin id, or listed twice");
+      seen |= 1u << order[k];
+      packed |= (uint32_t)order[k] << (4 * k);
+    }
+    if (seen != p->filter_mask) return fail(c, KAD_EINVAL, "filter order is not a permutation of the profile's filter mask");
+    if (n_units < 0 || (n_units && (!unit_idx || !out || !out->rejected || !out->feasible)))
+      return fail(c, KAD_EINVAL, "unit list or output view missing");
+    const int W = c->bd.W;
+    for (int i = 0; i < n_units; i++)
+      if (unit_idx[i] < 0 || unit_idx[i] >= W)
+        return fail(c, KAD_EINVAL, "unit_idx[" + std::to_string(i) + "] = " + std::to_string(unit_idx[i]) +
+                                       " outside the batch's " + std::to_string(W) + " units");
+    if (n_units == 0) return KAD_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t n = (size_t)n_units, C = (size_t)c->sd.C;
+    const size_t o_rej = 4 * n, o_feas = o_rej + 20 * n, o_fit = o_feas + 4 * n, o_ff = o_fit + 12 * n;
+    if (int r = grow(c, &c->d_explain, &c->explain_cap, o_ff + (out->first_fail ? n * C : 0))) return r;
+    char* d = static_cast<char*>(c->d_explain);
+    ExplainArgs a{};
+    a.s = c->sd;
+    a.b = c->bd;
+    a.filter_mask = p->filter_mask;
+    a.order = packed;
+    a.n_order = n_order;
+    a.units = reinterpret_cast<const int32_t*>(d);
+    a.n_units = n_units;
+    a.rejected = reinterpret_cast<int32_t*>(d + o_rej);
+    a.feasible = reinterpret_cast<int32_t*>(d + o_feas);
+    a.fit_detail = out->fit_detail ? reinterpret_cast<int32_t*>(d + o_fit) : nullptr;
+    a.first_fail = out->first_fail ? reinterpret_cast<uint8_t*>(d + o_ff) : nullptr;
+    HIPCHK(c, hipMemcpyAsync(d, unit_idx, 4 * n, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipEventRecord(c->xev[0], c->stream));
+    bool zeroed = false;
+    HIPCHK(c, launch_req_masks(c->sd, c->bd, c->stream, false, &zeroed));
+    HIPCHK(c, hipEventRecord(c->xev[1], c->stream));
+    HIPCHK(c, launch_explain(a, c->stream));
+    HIPCHK(c, hipEventRecord(c->xev[2], c->stream));
+    c->explained = true;
+    HIPCHK(c, hipMemcpyAsync(out->rejected, a.rejected, 20 * n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out->feasible, a.feasible, 4 * n, hipMemcpyDeviceToHost, c->stream));
+    if (a.fit_detail) HIPCHK(c, hipMemcpyAsync(out->fit_detail, a.fit_detail, 12 * n, hipMemcpyDeviceToHost, c->stream));
+    if (a.first_fail && C) HIPCHK(c, hipMemcpyAsync(out->first_fail, a.first_fail, n * C, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return KAD_OK;
+  });
+}
+
+int kad_explain_timing(kad_ctx* c, float ms[2]) {
+  if (!c || !ms) return KAD_EINVAL;
+  std::lock_guard<std::mutex> g(c->mu);
+  if (!c->explained) return fail(c, KAD_ESTATE, "no kad_explain ran");
+  HIPCHK(c, hipEventSynchronize(c->xev[2]));
+  HIPCHK(c, hipEventElapsedTime(&ms[0], c->xev[0], c->xev[1]));
+  HIPCHK(c, hipEventElapsedTime(&ms[1], c->xev[1], c->xev[2]));
+  return KAD_OK;
+}
 
 int kad_select_rows(kad_ctx* c, int n_rows, const int32_t* row_off, const int64_t* scores, const int64_t* maxc,
                     uint32_t pflags, int32_t* out_count, int32_t* out_sel, int32_t* out_status) {

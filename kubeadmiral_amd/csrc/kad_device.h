@@ -284,6 +284,24 @@ hipError_t launch_select_rows(int n_rows, const int32_t* row_off, const int64_t*
 hipError_t launch_plan_rows(const PlanRowsDev& r, int kmax, int force_ws, void* global_scratch, size_t scratch_bytes,
                             hipStream_t st);
 
+// kad_explain: the filter diagnosis of units[0 .. n_units) of the resident batch (kad_explain.hip). The
+// filter plugins run in the framework's order, four bits per position in `order` (KAD_PL_* ids, n_order of
+// them: a permutation of filter_mask's bits); outputs as kad_explain_view, in device memory.
+struct ExplainArgs {
+  SnapDev s;
+  BatchDev b;
+  uint32_t filter_mask;
+  uint32_t order;
+  int n_order;
+  const int32_t* units;
+  int n_units;
+  int32_t* rejected;    // [n_units][5]
+  int32_t* feasible;    // [n_units]
+  int32_t* fit_detail;  // [n_units][3] or null
+  uint8_t* first_fail;  // [n_units][C] or null
+};
+hipError_t launch_explain(const ExplainArgs& a, hipStream_t st);
+
 // kad_snapshot_update: scatter the changed clusters' columns of every snapshot
 // array from a resident delta blob into the resident snapshot blob.
 struct DeltaDev {

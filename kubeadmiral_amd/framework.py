@@ -181,6 +181,11 @@ class Framework:
     def replicas_plugin(self) -> int:
         return PLUGIN_ID[self.enabled.replicas_plugins[0]] if self.enabled.replicas_plugins else -1
 
+    def filter_order(self) -> List[int]:
+        """The KAD_PL_* ids of the filter plugins in the order RunFilterPlugins runs them
+        (``enabled.filter_plugins``, framework/runtime/framework.go:114-126): kad_explain's ``filter_order``."""
+        return [PLUGIN_ID[n] for n in self.enabled.filter_plugins]
+
     def has_filter(self, name) -> bool:
         return name in self.enabled.filter_plugins
 

@@ -10,6 +10,11 @@ import numpy as np
 from . import types as T
 from .pack import ST_ERR_REPLICAS, ST_ERR_SCORE, ST_ERR_SELECT, ST_NO_FEASIBLE, ST_OK, ST_STICKY, Batch
 
+# include/kad_sched.h enum kad_plugin, the filter plugins (ids 0..4)
+FILTER_NAMES = ("APIResources", "TaintToleration", "ClusterResourcesFit", "PlacementFilter", "ClusterAffinity")
+PL_FIT = 2
+NOT_REJECTED = 0xFF  # kad_explain_view.first_fail: the cluster passed every filter
+
 _ERR_STAGE = {ST_ERR_SCORE: "scoreClusters", ST_ERR_SELECT: "selectClusters", ST_ERR_REPLICAS: "replicaScheduling"}
 
 
@@ -58,6 +63,40 @@ class BatchResult:
         bad = np.zeros(W, bool)
         np.logical_or.at(bad, row[diff], True)
         return eq & ~bad
+
+
+@dataclass
+class FilterDiagnosis:
+    """kad_explain's outputs (include/kad_sched.h, kad_explain_view) for the listed units: row i belongs to
+    unit ``units[i]`` of the batch."""
+
+    units: np.ndarray                 # i32[n] unit indices
+    rejected: np.ndarray              # i32[n][5] clusters whose first failing filter is plugin id 0..4
+    feasible: np.ndarray              # i32[n] clusters passing every filter; -1 = sticky unit, not filtered
+    fit_detail: Optional[np.ndarray]  # i32[n][3] cpu, memory, any scalar short, among rejected[:, PL_FIT]
+    first_fail: Optional[np.ndarray]  # u8[n][C] plugin id, or NOT_REJECTED
+    order: List[int]                  # the framework's filter order (plugin ids)
+    n_clusters: int
+
+    def message(self, i: int) -> str:
+        """kube-scheduler's aggregate form for row i: "0/65 clusters are available: 31 ClusterAffinity, 12
+        TaintToleration, 9 ClusterResourcesFit (cpu 3, memory 8, scalar 1)" — plugins in framework order, zero
+        counts left out, the Fit resources only when ``fit_detail`` was collected."""
+        if int(self.feasible[i]) < 0:
+            return "sticky cluster: filters not run"
+        parts = []
+        for pl in self.order:
+            n = int(self.rejected[i][pl])
+            if n == 0:
+                continue
+            part = f"{n} {FILTER_NAMES[pl]}"
+            if pl == PL_FIT and self.fit_detail is not None:
+                short = [f"{name} {int(k)}" for name, k in zip(("cpu", "memory", "scalar"), self.fit_detail[i]) if k]
+                if short:
+                    part += " (" + ", ".join(short) + ")"
+            parts.append(part)
+        head = f"{int(self.feasible[i])}/{self.n_clusters} clusters are available"
+        return head + (": " + ", ".join(parts) if parts else "")
 
 
 def to_schedule_result(res: BatchResult, w: int, unit: T.SchedulingUnit, names: List[str]

@@ -20,7 +20,7 @@ import numpy as np
 from . import types as T
 from .framework import Framework
 from .pack import Batch, Snapshot, SnapshotDelta
-from .results import BatchResult, to_schedule_result
+from .results import BatchResult, FilterDiagnosis, to_schedule_result
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libkad.so")
@@ -39,6 +39,11 @@ class KadError(RuntimeError):
 class ResultView(ctypes.Structure):
     _fields_ = [("status", ctypes.c_void_p), ("count", ctypes.c_void_p), ("flags", ctypes.c_void_p),
                 ("cluster", ctypes.c_void_p), ("replicas", ctypes.c_void_p)]
+
+
+class ExplainView(ctypes.Structure):  # kad_explain_view
+    _fields_ = [("rejected", ctypes.c_void_p), ("feasible", ctypes.c_void_p), ("fit_detail", ctypes.c_void_p),
+                ("first_fail", ctypes.c_void_p)]
 
 
 class ResultState(ctypes.Structure):  # kad_result_state
@@ -94,6 +99,9 @@ def load_library(path: str = LIB_PATH):
     L.kad_select_rows.argtypes = [P, I, P, P, P, U32, P, P, P]
     L.kad_plan_rows.argtypes = [P, I, P, P, P, P, P, P, P, P, P, P, P, P]
     L.kad_debug_scores.argtypes = [P, P, P, P]
+    if hasattr(L, "kad_explain"):  # (absent from libraries of older revisions: A/B runs)
+        L.kad_explain.argtypes = [P, P, P, I, P, I, P]
+        L.kad_explain_timing.argtypes = [P, P]
     L.kad_debug_inject_fault.argtypes = [P, I]
     L.kad_debug_plan_force_workspace.argtypes = [P, I]
     L.kad_trigger_suffix_upload.argtypes = [P, P, SZ]
@@ -331,6 +339,36 @@ class Context:
         prof = fwk.to_c()
         self._chk(self.L.kad_debug_scores(self.h, ctypes.byref(prof), _p(feas), _p(tot)))
         return feas[:W * C].reshape(W, C), tot[:W * C].reshape(W, C)
+
+    def explain(self, fwk: Framework, units=None, per_cluster: bool = False, fit_detail: bool = True
+                ) -> FilterDiagnosis:
+        """kad_explain: per listed unit of the uploaded batch (``units=None``: all of them), how many clusters
+        each filter plugin of ``fwk`` rejected — each cluster counted for the first plugin that fails in the
+        framework's order — and how many passed; ``per_cluster`` adds the rejecting plugin per cluster. Works
+        before or after schedule() and changes nothing a later schedule() or download() sees."""
+        W, C = self.batch.W, self.snap.C
+        idx = np.arange(W, dtype=np.int32) if units is None else np.ascontiguousarray(units, np.int32).reshape(-1)
+        n = len(idx)
+        order = fwk.filter_order()
+        ord_a = np.array(order or [0], np.int32)
+        rej = np.zeros((max(1, n), 5), np.int32)
+        feas = np.zeros(max(1, n), np.int32)
+        fit = np.zeros((max(1, n), 3), np.int32) if fit_detail else None
+        ff = np.zeros((max(1, n), max(1, C)), np.uint8) if per_cluster else None
+        v = ExplainView(rej.ctypes.data, feas.ctypes.data, None if fit is None else fit.ctypes.data,
+                        None if ff is None else ff.ctypes.data)
+        prof = fwk.to_c()
+        self._chk(self.L.kad_explain(self.h, ctypes.byref(prof), _p(ord_a), len(order), _p(idx) if n else None, n,
+                                     ctypes.byref(v)))
+        if ff is not None:  # the library wrote n rows of C bytes at the start of the buffer
+            ff = ff.reshape(-1)[:n * C].reshape(n, C).copy()
+        return FilterDiagnosis(idx, rej[:n], feas[:n], None if fit is None else fit[:n], ff, order, C)
+
+    def explain_timing(self):
+        """kad_explain_timing: device ms of the last explain() — (requirement rows, filter_explain_kernel)."""
+        ms = (ctypes.c_float * 2)()
+        self._chk(self.L.kad_explain_timing(self.h, ms))
+        return float(ms[0]), float(ms[1])
 
     def select_rows(self, rows: Sequence[Sequence[int]], max_clusters: Sequence[Optional[int]], flags: int = 0):
         """MaxCluster on explicit score rows → per row (status, sorted selected positions)."""

@@ -7,7 +7,7 @@ repo=$(cd "$(dirname "$0")/.." && pwd)
 d=$(mktemp -d); mkdir -p "$repo/ablibs"
 git -C "$repo" archive "$rev" kubeadmiral_amd/csrc include | tar x -C "$d"
 cd "$d/kubeadmiral_amd/csrc"
-for f in kad_kernels.hip kad_trigger.hip kad_delta.hip kad_diff.hip kad_api.hip kad_pack.cpp kad_objects.cpp; do
+for f in *.hip *.cpp; do
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -w -pthread -c $f -o "$d/$f.o" &
 done
 for j in $(jobs -p); do wait $j || { echo "compile failed" >&2; exit 1; }; done
