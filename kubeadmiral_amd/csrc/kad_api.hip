@@ -150,6 +150,10 @@ static const T* at(const void* base, const uint64_t* off, int i) {
   return reinterpret_cast<const T*>(static_cast<const char*>(base) + off[i]);
 }
 
+// bytes allocated past the snapshot blob: at C = 0 every array is empty and starts at the blob's end, and the
+// kernels' clamped loads (cluster index 0 for lanes past C) read one element there
+constexpr size_t SNAP_PAD = 64;
+
 static int grow(kad_ctx* c, void** p, size_t* cap, size_t need) {
   if (need <= *cap && *p) return 0;
   if (*p) (void)hipFree(*p);
@@ -730,7 +734,7 @@ static int snapshot_upload_locked(kad_ctx* c, const void* blob, size_t nbytes) {
   // overwritten: nothing may run on them until every step below has succeeded
   invalidate_snapshot(c);
   HIPCHK(c, hipSetDevice(c->device));
-  if (int r = grow(c, &c->d_snap, &c->snap_bytes, nbytes)) return r;
+  if (int r = grow(c, &c->d_snap, &c->snap_bytes, nbytes + SNAP_PAD)) return r;
   HIPCHK(c, hipMemcpyAsync(c->d_snap, blob, nbytes, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->snap_hdr = h;
@@ -754,7 +758,7 @@ static int snapshot_from_peer_locked(kad_ctx* c, kad_ctx* src) {
   invalidate_snapshot(c);
   const size_t nbytes = src->snap_hdr.total_bytes;
   HIPCHK(c, hipSetDevice(c->device));
-  if (int r = grow(c, &c->d_snap, &c->snap_bytes, nbytes)) return r;
+  if (int r = grow(c, &c->d_snap, &c->snap_bytes, nbytes + SNAP_PAD)) return r;
   if (c->device == src->device)
     HIPCHK(c, hipMemcpyAsync(c->d_snap, src->d_snap, nbytes, hipMemcpyDeviceToDevice, c->stream));
   else
@@ -778,7 +782,7 @@ int kad_snapshot_upload_device(kad_ctx* c, const void* dev_blob, size_t nbytes) 
     HIPCHK(c, hipMemcpy(&h, dev_blob, sizeof(h), hipMemcpyDeviceToHost));
     if (int r = check_snapshot_header(c, h, nbytes)) return r;
     invalidate_snapshot(c);
-    if (int r = grow(c, &c->d_snap, &c->snap_bytes, nbytes)) return r;
+    if (int r = grow(c, &c->d_snap, &c->snap_bytes, nbytes + SNAP_PAD)) return r;
     HIPCHK(c, hipMemcpyAsync(c->d_snap, dev_blob, nbytes, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->snap_hdr = h;

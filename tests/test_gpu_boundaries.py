@@ -1,0 +1,271 @@
+"""HIP path == the C oracle at every cluster count C where a launcher changes kernels, bit for bit.
+
+nch = ceil(C / 64) decides the route (kad_kernels.hip launch_prep / launch_schedule / launch_rows /
+launch_defer_pass, kad_explain.hip launch_explain); each boundary below is run on both of its sides, and the
+route is asserted from the library's own reporting (snapshot_paths, path_counts):
+
+  nch 1..4 (C <= 256)          schedule_lean_kernel<1..4, clean>; <4, true, SM_LEAST> for C2's profile
+  nch 4 -> 5 (C 256 -> 257)    lean -> schedule_wide_kernel, on clean snapshots
+  nch == 8 (C 449..512)        schedule_wide_kernel<8, 8, SM_DEFAULT> under the default score set
+  nch == 16 (C 961..1024)      schedule_wide_kernel<16, 0, SM_LEAST> under LeastAllocated alone, folded
+  nch 16 -> 17 (C 1024 -> 1025) wide -> schedule_lean_kernel<0> + schedule_row_kernel + the defer pass
+  nch 64 -> 65, 128 -> 129, 192 -> 193, 256 -> 257 (C 4096 / 4097, 8192 / 8193, 12288, 16384 / 16385)
+                               prep_kernel -> prep_wave_kernel<2> -> <3> -> <4> -> prep_kernel
+  C 12288 -> past it           ROW_MAX_C: long lists leave schedule_row_kernel for the full kernel
+  C 16384 -> 16385             FITFOLD_MAX_C: no fit threshold rows past it
+  C 32768 -> 32769             filter_explain_kernel: 4 waves per block -> 1
+  C = 65535                    the ABI's maximum, the largest u16 cluster id
+  feasible lists 256 / 512     registers -> schedule_row_kernel (lean<0>: n > 256; wide: n > WIDE_P = 512)
+
+Exact chunk multiples have no tail chunk; one past them has one live lane in the last chunk. The inputs come
+from gpu_util (built once, shared with test_boundary_inputs.py, which checks on the oracle alone that they
+put results on the edges). Every comparison is exact.
+"""
+
+import functools
+
+import numpy as np
+import pytest
+
+import gpu_util as G
+from gpu_util import assert_same, c_oracle, nch_of
+from kubeadmiral_amd import framework as F
+from kubeadmiral_amd import pack, synth
+from kubeadmiral_amd import types as T
+
+pytestmark = pytest.mark.gpu
+
+ROW_MAX_C = 12288       # kad_kernels.hip
+FITFOLD_MAX_C = 16384   # kad_device.h
+WIDE_P = 512            # kad_device.h
+LEAN_P = 256            # schedule_lean_kernel<0>: 64 * LEAN_QMAX_DYN register positions
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    from kubeadmiral_amd import build, runtime
+    build.build()
+    c = runtime.Context(0)
+    yield c
+    c.close()
+
+
+@pytest.fixture
+def case(request):
+    """The inputs of one case, built (or taken from gpu_util's caches) in the test's setup phase."""
+    fn, *args = request.param
+    return fn(*args)
+
+
+def route(C):
+    """The kernels a clean snapshot of C clusters takes, as the test ids name them."""
+    nch = nch_of(C)
+    sched = f"lean{nch}" if nch <= 4 else ("wide" if nch <= 16 else "lean0")
+    cw = (nch + 63) // 64
+    return f"C{C}-nch{nch}-{sched}-{f'prepwave{cw}' if nch > 64 and cw <= 4 else 'prep'}"
+
+
+def run(ctx, snap, batch, fwk):
+    ctx.upload_snapshot(snap)
+    return ctx.run(fwk, batch)
+
+
+def assert_clean_route(ctx, C, W, klass="strict"):
+    paths, counts = ctx.snapshot_paths(), ctx.path_counts()
+    assert paths["resource_class"] == klass, paths
+    assert paths["wide"] == (5 <= nch_of(C) <= 16), paths
+    assert paths["fitfold"] == (C <= FITFOLD_MAX_C), paths
+    assert counts["units"] == W, counts
+    return paths, counts
+
+
+# ------------------------------------------------------------------ (a) C sweep
+SWEEP = [(C, which) for C in G.SWEEP_CS for which in G.SWEEP_PROFILES]
+
+
+@pytest.mark.parametrize("case,C,which", [((G.sweep_case, C, which), C, which) for C, which in SWEEP],
+                         ids=[f"{route(C)}-{which}" for C, which in SWEEP], indirect=["case"])
+def test_c_sweep(ctx, case, C, which):
+    """gen_fuzz(W = 64) plus four probe units (placement {C-1}, {64 * (nch - 1)}, {0}, and one every cluster
+    is feasible for) under the default set, no plugins at all (count == C, no ghost lane c >= C may appear)
+    and a rotating fuzz profile. The probe with all C clusters feasible is a list past the registers of every
+    kernel once C > 512 (wide) or C > 256 (lean<0>): it must reach schedule_row_kernel up to ROW_MAX_C =
+    12288 and the full kernel past it; below those sizes nothing may."""
+    snap, batch, fwk, want = case
+    got = run(ctx, snap, batch, fwk)
+    paths, counts = assert_clean_route(ctx, C, G.SWEEP_W + 4)
+    assert paths["fold"], paths
+    nch = nch_of(C)
+    if C > (WIDE_P if nch <= 16 else LEAN_P):
+        if C <= ROW_MAX_C:
+            assert counts["row_kernel"] > 0, counts
+        else:
+            assert counts["row_kernel"] == 0 and counts["full_kernel"] > 0, counts
+    else:
+        assert counts["row_kernel"] == 0, counts
+    assert_same(got, want, f"sweep {route(C)} {which}")
+
+
+# ------------------------------------------- (b) specialised instantiations, both ends of their range
+SPECIAL = [(prof, C, zero, relaxed) for prof, Cs in (("c3", (961, 1024)), ("default", (449, 512)), ("c2", (193, 256)))
+           for C in Cs for zero in (False, True) for relaxed in (False, True)]
+
+
+@functools.lru_cache(maxsize=None)
+def special_case(prof, C, zero, relaxed):
+    seed = 8300 + C
+    clusters, units = synth.gen_fuzz(seed, W=90, C=C)
+    if relaxed:  # as test_fuzz_relaxed_snapshot_gpu_equals_c_oracle: over-committed and empty clusters
+        synth.production_resources(clusters, np.random.default_rng(seed), p_over=0.2, p_empty=0.1)
+        clusters[0].allocatable, clusters[0].available = {}, {}
+        clusters[1].available = dict(clusters[1].available, cpu="-5", memory="-1Gi")
+    if zero:  # as test_zero_request_batches_gpu_equals_c_oracle: BatchDev::zero_req
+        for su in units:
+            su.resource_request = T.Resource()
+    fwk = G.default_framework() if prof == "default" else synth.profile_for(prof)
+    snap = pack.Snapshot(clusters)
+    batch = pack.Batch(snap, fwk, units)
+    return snap, batch, fwk, c_oracle(snap, batch, fwk)
+
+
+@pytest.mark.parametrize("case,prof,C,zero,relaxed", [((special_case, *s), *s) for s in SPECIAL], indirect=["case"],
+                         ids=[f"{p}-{route(C)}-{'zeroreq' if z else 'requests'}-{'relaxed' if r else 'clean'}"
+                              for p, C, z, r in SPECIAL])
+def test_specialised_instantiations(ctx, case, prof, C, zero, relaxed):
+    """schedule_wide_kernel<16, 0, SM_LEAST> (C3's profile, nch == 16: C = 961 and 1024),
+    schedule_wide_kernel<8, 8, SM_DEFAULT> (the default set, nch == 8: C = 449 and 512) and
+    schedule_lean_kernel<4, true, SM_LEAST> (C2's profile, nch == 4: C = 193 and 256), each with requests and
+    as a zero-request batch (the <..., true> instantiations of the wide kernel), on a strict and on a relaxed
+    snapshot. launch_schedule picks them from nch, the score mask and fold && fitfold, all asserted here."""
+    snap, batch, fwk, want = case
+    got = run(ctx, snap, batch, fwk)
+    paths, _ = assert_clean_route(ctx, C, 90, "relaxed" if relaxed else "strict")
+    assert paths["exact_f64"] and paths["fold"] and paths["fitfold"], paths
+    assert nch_of(C) == {"c3": 16, "default": 8, "c2": 4}[prof]
+    least = 1 << F.PLUGIN_ID[F.ClusterResourcesLeastAllocated]
+    assert (fwk.to_c().score_mask == least) == (prof != "default")
+    assert_same(got, want, f"{prof} C={C} zero={zero} relaxed={relaxed}")
+
+
+# ------------------------------------------------------- (c) generic snapshots on the middle sizes
+GENERIC = [(C, which) for C in (257, 320, 1024) for which in ("default", "fuzz")]
+
+
+@functools.lru_cache(maxsize=None)
+def generic_case(C, which):
+    clusters, units = G.extreme_batch(8400 + C, C=C, W=90)
+    fwk = G.default_framework() if which == "default" else synth.fuzz_framework(5 if C == 320 else 3)
+    snap = pack.Snapshot(clusters)
+    batch = pack.Batch(snap, fwk, units)
+    return snap, batch, fwk, c_oracle(snap, batch, fwk)
+
+
+@pytest.mark.parametrize("case,C,which", [((generic_case, *g), *g) for g in GENERIC], indirect=["case"],
+                         ids=[f"C{C}-nch{nch_of(C)}-lean0-generic-{w}" for C, w in GENERIC])
+def test_generic_snapshots_on_the_middle_sizes(ctx, case, C, which):
+    """extreme_batch's cluster edits (capacities past 2^46, zero and huge cpu) make the snapshot generic, and
+    a generic snapshot of 5 <= nch <= 16 goes to schedule_lean_kernel<0, false>, not the wide kernel."""
+    snap, batch, fwk, want = case
+    got = run(ctx, snap, batch, fwk)
+    paths, counts = ctx.snapshot_paths(), ctx.path_counts()
+    assert paths["resource_class"] == "generic" and paths["wide"] is False and not paths["exact_f64"], paths
+    assert counts["units"] == 90 and counts["row_kernel"] == 0, counts
+    assert_same(got, want, f"generic C={C} {which}")
+
+
+# ------------------------------------------------------------ (d) exact feasible-list lengths
+@pytest.mark.parametrize("case,C", [((G.list_case, C), C) for C in G.LIST_CS], indirect=["case"],
+                         ids=[f"{route(C)}-cut{WIDE_P if nch_of(C) <= 16 else LEAN_P}" for C in G.LIST_CS])
+def test_exact_feasible_list_lengths(ctx, case, C):
+    """Placement-only units with exactly n feasible clusters, n in {0, 1, 63, 64, 65, 255, 256, 257, 511,
+    512, 513, C-1, C}, as the first n, the last n and n strided clusters; MaxClusters None, 1, n - 1.
+
+    The routing rules, read from the code: on the wide path (C = 1000) prep_kernel routes a unit to
+    schedule_row_kernel when its static words hold cnt > WIDE_P = 512 clusters (kad_kernels.hip prep_kernel
+    `cnt > WIDE_P`; without early routing the wide kernel does the same in wide_row_or_defer). On
+    schedule_lean_kernel<0> (C = 1100) the rule is `NCH == 0 && n > P` with P = 64 * lean_qmax(0) = 64 *
+    LEAN_QMAX_DYN = 256: a list of 257 or more goes to lean_row_or_defer, the row list when
+    BatchDev::use_rows (clean, fold, fitfold, C <= ROW_MAX_C: asserted). 256 resp. 512 clusters stay in
+    registers."""
+    snap, batch, fwk, want, meta = case
+    got = run(ctx, snap, batch, fwk)
+    paths, counts = assert_clean_route(ctx, C, len(meta))
+    assert paths["exact_f64"] and paths["fold"] and paths["fitfold"] and C <= ROW_MAX_C, paths
+    cut = WIDE_P if paths["wide"] else LEAN_P
+    assert cut == (WIDE_P if C == 1000 else LEAN_P)
+    assert counts["row_kernel"] == sum(n > cut for n, _ in meta), counts
+    assert counts["full_kernel"] == 0, counts
+    assert_same(got, want, f"lists C={C}")
+
+
+# ------------------------------------------------------------ (e) small W on the wide path
+@functools.lru_cache(maxsize=None)
+def small_w_case(W):
+    _, units, snap = G.fuzz_with_probes(G.SWEEP_SEEDS[320], 320, max(G.SMALL_WS))
+    fwk = G.default_framework()
+    batch = pack.Batch(snap, fwk, units[:W])
+    return snap, batch, fwk, c_oracle(snap, batch, fwk)
+
+
+@pytest.mark.parametrize("case,W", [((small_w_case, W), W) for W in G.SMALL_WS], indirect=["case"],
+                         ids=[f"C320-nch5-wide-W{W}" for W in G.SMALL_WS])
+def test_small_batches_on_the_wide_path(ctx, case, W):
+    """Fewer units than one block's 16 waves, one more, and one past a 64-unit head of the work queue: the
+    first W units of one fuzz batch at C = 320 under the default profile."""
+    snap, batch, fwk, want = case
+    assert batch.W == W
+    got = run(ctx, snap, batch, fwk)
+    assert_clean_route(ctx, 320, W)
+    assert_same(got, want, f"wide W={W}")
+
+
+# ------------------------------------------------------------------------ (f) the limits
+@pytest.mark.parametrize("case", [(G.max_c_case,)], indirect=True, ids=[route(G.MAX_C)])
+def test_max_cluster_count(ctx, case):
+    """C = 65535: cluster ids up to 0xFFFE in the u16 position lists; the unconstrained probe selects all of
+    them (the full kernel: C is past ROW_MAX_C)."""
+    snap, batch, fwk, want = case
+    got = run(ctx, snap, batch, fwk)
+    paths, counts = ctx.snapshot_paths(), ctx.path_counts()
+    assert paths["resource_class"] == "strict" and paths["wide"] is False and not paths["fitfold"], paths
+    assert counts["units"] == 12 and counts["row_kernel"] == 0 and counts["full_kernel"] > 0, counts
+    assert_same(got, want, "C=65535")
+    assert int(got.count[11]) == G.MAX_C
+
+
+@pytest.mark.parametrize("case", [(G.zero_c_case,)], indirect=True, ids=["C0-nch0-lean0-prep"])
+def test_no_clusters(ctx, case):
+    """C = 0: every unit ends with the oracle's no-feasible status."""
+    snap, batch, fwk, want = case
+    got = run(ctx, snap, batch, fwk)
+    assert ctx.snapshot_paths()["wide"] is False and ctx.path_counts()["units"] == 4
+    assert (want.status == pack.ST_NO_FEASIBLE).all()
+    assert_same(got, want, "C=0")
+
+
+# ----------------------------------------------------------------- (g) kad_explain boundaries
+EXPLAIN = [(11, 64, 9, 60), (12, 128, 9, 60), (13, 4096, 9, 8), (14, 32768, 9, 2), (15, 32769, 9, 2)]
+
+
+@functools.lru_cache(maxsize=None)
+def explain_case(*case):
+    import test_gpu_explain as TE
+    clusters, units, _ = TE.inputs(*case)
+    return TE.oracle_explain(clusters, units, TE.DEFAULT)
+
+
+@pytest.mark.parametrize("case,key", [((explain_case, *e), e) for e in EXPLAIN], indirect=["case"],
+                         ids=[f"seed{s}-C{C}-nch{nch_of(C)}-W{W}-{'1wave' if C > 32768 else '4waves'}"
+                              for s, C, _, W in EXPLAIN])
+def test_explain_boundaries(ctx, case, key):
+    """filter_explain_kernel at exact chunk multiples (C = 64, 128, 4096: no tail chunk, and exactly one
+    64-chunk ClusterAffinity window) and on both sides of launch_explain's waves-per-block switch
+    (C <= 32768: 4 waves per block; C = 32769: 1), with the rejecting plugin per cluster."""
+    import test_gpu_explain as TE
+    fwk = TE.framework(TE.DEFAULT)
+    clusters, units, _, _ = TE.upload(ctx, key, fwk)
+    d = ctx.explain(fwk, per_cluster=True)
+    assert d.first_fail.shape == (len(units), len(clusters)) == (key[3], key[1])
+    TE.assert_diag(d, case)
+    sticky = np.array([bool(su.sticky_cluster and su.current_clusters) for su in units])
+    assert (d.rejected.sum(1) + d.feasible == key[1])[~sticky].all()

@@ -16,6 +16,7 @@ import pytest
 
 from golden_util import case_id, load
 from gpu_util import assert_same, c_oracle
+from gpu_util import extreme_batch as _extreme_batch
 from kubeadmiral_amd import framework as F
 from kubeadmiral_amd import k8s, pack, synth
 from kubeadmiral_amd import types as T
@@ -529,33 +530,6 @@ def test_tie_heavy_selection_rows(ctx):
 
 
 # ------------------------------------------------------- extreme values
-def _extreme_batch(seed, C=200, W=120):
-    """Fuzz batch pushed to the edges of the lean kernel's fast paths: capacities
-    above 2^46 (Least/MostAllocated's exact int64 path), zero and negative
-    quantities, and preferred-affinity weights of +-2^31 so totals span more
-    than 2^32 (64-bit bisection; wide-key straddles go to the full kernel)."""
-    rng = np.random.default_rng(seed)
-    clusters, units = synth.gen_fuzz(seed, W=W, C=C)
-    for c in clusters:
-        r = rng.random()
-        if r < 0.25:
-            c.allocatable["memory"] = str(int(rng.integers(1 << 46, 1 << 52)))
-            c.available["memory"] = str(int(rng.integers(0, 1 << 46)))
-        elif r < 0.35:
-            c.allocatable["cpu"] = "0"
-            c.available["cpu"] = "0"
-        elif r < 0.45:
-            c.allocatable["cpu"] = f"{int(rng.integers(1, 1 << 40))}m"
-            c.available["cpu"] = "1m"
-    for su in units:
-        ca = su.affinity.cluster_affinity if su.affinity is not None else None
-        if ca is not None and ca.preferred:
-            for p in ca.preferred:
-                if rng.random() < 0.5:
-                    p.weight = int(rng.choice([-(1 << 31), (1 << 31) - 1, -123456789, 987654321]))
-    return clusters, units
-
-
 @pytest.mark.parametrize("seed", range(8))
 def test_extreme_values_gpu_equals_c_oracle(ctx, seed):
     clusters, units = _extreme_batch(500 + seed)
