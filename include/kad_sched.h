@@ -470,6 +470,99 @@ int kad_explain(kad_ctx* ctx, const kad_profile* profile, const int32_t* filter_
  * ms[0] = the requirement rows' rebuild, ms[1] = filter_explain_kernel. No reference counterpart. */
 int kad_explain_timing(kad_ctx* ctx, float ms[2]);
 
+/* ------------------------------------------------------ override policies
+ * The controller that runs after the scheduler on every federated object is the override-policy controller
+ * (pkg/controllers/override/overridepolicy_controller.go:254-376). Per object it looks up at most two
+ * policies (the ClusterOverridePolicy, then the OverridePolicy: lookForMatchedPolicies, override/util.go:45-97)
+ * and, for every placed cluster and every override rule, asks isClusterMatched (util.go:154-221) whether the
+ * rule's TargetClusters select the cluster (parseOverrides, util.go:99-140). That is the (object, cluster)
+ * selector evaluation of ClusterAffinity again, so the same requirement rows serve it: the policies' distinct
+ * requirements are evaluated once per cluster, each rule becomes two cluster rows (matches, errors), and a
+ * batch of objects only gathers bits of those rows at its placed clusters.
+ *
+ * isClusterMatched per rule and cluster, an AND with this short-circuit:
+ *   TargetClusters == nil          matches every cluster;
+ *   Clusters                       empty: any cluster; else the name must be listed (a miss is false, no error,
+ *                                  whatever the selector below looks like);
+ *   ClusterSelector                metav1.LabelSelectorAsSelector{MatchLabels}: validates keys and values (an
+ *                                  invalid map is an ERROR, unlike the scheduler's SelectorFromSet), else an AND
+ *                                  of equals;
+ *   ClusterAffinity                empty: any cluster; else MatchClusterSelectorTerms
+ *                                  (clusterselector/util.go:97-132), whose errors (invalid expressions or fields of
+ *                                  a term that the cluster reaches) are ERRORS here, not "false".
+ * parseOverrides fails for an object iff some (placed cluster, rule) pair errors, or a rule that matches a placed
+ * cluster carries a JSON-patch value that does not unmarshal (util.go:125-131, 223-240).
+ *
+ * Policy-set blob (packed against one snapshot, kubeadmiral_amd/overrides.py PolicySet): P policies, policy p's
+ * rules are [POL_RULE_OFF[p], POL_RULE_OFF[p+1]) of the R rules; requirements are interned set-wide and
+ * encoded exactly as KAD_B_REQ; a rule's target program has the filter-program format above
+ * (n_sel, selector ids, req_present, [n_terms, terms with KAD_TERM_* flags]); an invalid selector carries no
+ * requirements (KAD_OVR_SEL_INVALID).                                                                      */
+#define KAD_OVERRIDE_MAGIC 0x4F44414Bu /* "KADO" */
+enum kad_override_array {
+  KAD_O_POL_RULE_OFF = 0, /* i32[P+1]                                                         */
+  KAD_O_RULE_FLAGS,       /* u32[R]   KAD_OVR_*                                               */
+  KAD_O_RULE_NAME_OFF,    /* i32[R+1] TargetClusters.Clusters as snapshot ids                 */
+  KAD_O_RULE_NAME,        /* i32[]    sorted, unique; names the snapshot lacks are dropped    */
+  KAD_O_RULE_PROG_OFF,    /* i32[R+1]                                                         */
+  KAD_O_RULE_PROG,        /* i32[]    target programs                                         */
+  KAD_O_REQ_OFF,          /* i32[NR+1]                                                        */
+  KAD_O_REQ,              /* i32[]    requirement words (KAD_OP_*)                            */
+  KAD_O_NARRAYS
+};
+#define KAD_OVR_HAS_TARGET 1u  /* TargetClusters != nil                                              */
+#define KAD_OVR_HAS_NAMES 2u   /* len(Clusters) > 0 (a list whose names are all unknown matches nothing) */
+#define KAD_OVR_SEL_INVALID 4u /* LabelSelectorAsSelector(ClusterSelector) returns an error          */
+#define KAD_OVR_BAD_VALUE 8u   /* some JsonPatch value (non-empty raw bytes) does not unmarshal      */
+typedef struct kad_override_header {
+  uint32_t magic;
+  uint32_t abi_version;
+  int32_t n_policies; /* P  */
+  int32_t n_rules;    /* R  */
+  int32_t n_reqs;     /* NR */
+  int32_t n_clusters; /* must equal the snapshot's C */
+  uint64_t total_bytes;
+  uint64_t snapshot_fingerprint;
+  uint64_t off[KAD_O_NARRAYS];
+} kad_override_header;
+
+/* Validates every offset, id and program length (KAD_EINVAL), then keeps the set resident. Needs a resident
+ * snapshot with the blob's fingerprint. kad_snapshot_update keeps the set (its rows are rebuilt from the
+ * snapshot's current labels by every kad_override_match); kad_snapshot_upload drops it, as it drops the batch. */
+int kad_override_policies_upload(kad_ctx* ctx, const void* blob, size_t nbytes);
+/* Host only (no device): the same validation against the header of a packed snapshot blob. */
+int kad_override_policies_check(const void* blob, size_t nbytes, const void* snapshot_blob, size_t snapshot_nbytes);
+
+/* A batch of objects. obj_policy[i][0] is object i's ClusterOverridePolicy and [i][1] its OverridePolicy, as
+ * indices into the uploaded set (-1: none); the object's rule list is the first policy's rules followed by the
+ * second's. Placed clusters: place_off / place_cluster (snapshot ids, unique per object, any order; -1 = a
+ * name the snapshot does not know: matches nothing, errors nothing), or place_off == NULL: the resident
+ * results of the last kad_schedule (KAD_ESTATE if nothing was scheduled), n_objects = the resident batch's
+ * units, object i = unit i. Then the slot space is the batch's output slots followed by its KAD_B_CUR_ID
+ * entries: unit i's placed clusters are slots [OUT_OFF[i], OUT_OFF[i] + count[i]) when its status is KAD_ST_OK,
+ * slots n_out_slots + [CUR_OFF[i], CUR_OFF[i+1]) when it is sticky (KAD_ST_STICKY), none otherwise
+ * (KAD_ST_NO_FEASIBLE, errors); n_slots = n_out_slots + CUR_OFF[W] (a kad_group member: of its shard).     */
+typedef struct kad_override_batch {
+  int32_t n_objects;
+  int32_t rule_words;           /* RW: u32 words per slot row; every object's rule count must be <= 32*RW */
+  const int32_t* obj_policy;    /* [n_objects][2] */
+  const int32_t* place_off;     /* [n_objects + 1] or NULL */
+  const int32_t* place_cluster; /* [place_off[n_objects]] */
+} kad_override_batch;
+typedef struct kad_override_view {
+  int32_t* status;   /* [n_objects] 0 = OK, 1 = the first policy failed, 2 = the second policy failed      */
+  uint32_t* matched; /* [n_slots][RW] bit j: rule j of the object's rule list matches the slot's cluster;
+                        all zero for failed objects and for slots that hold no placed cluster            */
+} kad_override_view;
+/* Runs on the ctx stream (requirement rows of the set, override_rule_rows_kernel, override_status_kernel +
+ * override_match_kernel: kad_override.hip); blocks until the outputs are in the caller's buffers. Leaves the
+ * last results, the timings and any later kad_schedule as they were, like kad_explain. Members of a
+ * kad_group: through kad_group_member (objects = the member's shard of units). */
+int kad_override_match(kad_ctx* ctx, const kad_override_batch* batch, const kad_override_view* out);
+/* Device time of the last kad_override_match that launched, from HIP events: ms[0] = the set's requirement
+ * rows, ms[1] = the rule rows, ms[2] = the status + match kernels. No reference counterpart. */
+int kad_override_timing(kad_ctx* ctx, float ms[3]);
+
 /* ------------------------------------------------ result application (§8 f3)
  * applySchedulingResult (pkg/controllers/scheduler/scheduler.go:632-695) writes a unit's result into its
  * federated object: the scheduler controller's placement (util.SetPlacementClusterNames,

@@ -87,6 +87,24 @@ struct kad_ctx {
   size_t explain_cap = 0;
   hipEvent_t xev[3] = {nullptr, nullptr, nullptr};  // kad_explain: start, after the requirement rows, end
   bool explained = false;     // xev hold a kad_explain run
+  // override policies (kad_override_*): the resident policy-set blob, its requirement routing (the layout of
+  // h_reqseg), its rows (requirement rows [NR][nch], then M and E [R][nch] each) and one match call's buffers
+  void* d_ovr = nullptr;
+  size_t ovr_cap = 0;
+  kad_override_header ovr_hdr{};
+  bool have_ovr = false;
+  std::vector<int32_t> h_ovr_pro;  // POL_RULE_OFF (host copy: rule counts per object are checked per call)
+  std::vector<int32_t> h_ovr_reqseg;
+  void* d_ovr_reqseg = nullptr;
+  size_t ovr_reqseg_cap = 0;
+  int ovr_n_seg = 0, ovr_n_rowreq = 0, ovr_n_seg_reqs = 0;
+  void* d_ovr_rows = nullptr;
+  size_t ovr_rows_cap = 0;
+  void* d_ovr_work = nullptr;
+  size_t ovr_work_cap = 0;
+  hipEvent_t oev[4] = {nullptr, nullptr, nullptr, nullptr};  // start, after requirement rows, after rule rows, end
+  bool ovr_ran = false;       // oev hold a kad_override_match run
+  int32_t cur_lo = 0, cur_n = 0;  // the resident batch's (shard's) range of KAD_B_CUR_ID entries
   // HIP event records around the stages (kad_set_timing); timed = the last
   // kad_schedule recorded them
   bool timing = false, timed = false;
@@ -453,6 +471,11 @@ int kad_ctx_create(int hip_device, kad_ctx** out) {
       kad_ctx_destroy(c);
       return KAD_EHIP;
     }
+  for (auto& e : c->oev)
+    if (hipEventCreate(&e) != hipSuccess) {
+      kad_ctx_destroy(c);
+      return KAD_EHIP;
+    }
   *out = c;
   return KAD_OK;
 }
@@ -464,13 +487,16 @@ int kad_ctx_destroy(kad_ctx* c) {
   if (c->side) (void)hipStreamSynchronize(c->side);  // the row kernel may run there: drain it before any free
   for (void* p : {c->d_snap, c->d_batch, (void*)c->d_plan_rows, c->d_plan_hdr, c->d_plan_big, (void*)c->d_req_mask, (void*)c->d_status, (void*)c->d_count,
                   (void*)c->d_cluster, (void*)c->d_flags, (void*)c->d_replicas, c->d_scratch, c->d_rec, c->d_delta, c->d_sw, c->d_cw, c->d_defer, c->d_wq, c->d_slices, c->d_fit, c->d_reqseg, c->d_rowslab, c->d_vrows, c->d_rescols,
-                  c->t_suffix, c->t_prefix, c->t_work, c->t_tabs, c->d_diff, c->d_explain})
+                  c->t_suffix, c->t_prefix, c->t_work, c->t_tabs, c->d_diff, c->d_explain, c->d_ovr, c->d_ovr_reqseg,
+                  c->d_ovr_rows, c->d_ovr_work})
     if (p) (void)hipFree(p);
   for (auto& e : c->ev)
     if (e) (void)hipEventDestroy(e);
   for (auto& e : c->tev)
     if (e) (void)hipEventDestroy(e);
   for (auto& e : c->xev)
+    if (e) (void)hipEventDestroy(e);
+  for (auto& e : c->oev)
     if (e) (void)hipEventDestroy(e);
   if (c->side) {
     (void)hipStreamSynchronize(c->side);
@@ -714,6 +740,7 @@ static void invalidate_snapshot(kad_ctx* c) {
   c->have_snapshot = false;
   c->have_batch = false;
   c->ran = false;
+  c->have_ovr = false;  // a policy set is packed against the snapshot's vocabulary, like a batch
 }
 
 static int snapshot_upload_locked(kad_ctx* c, const void* blob, size_t nbytes);
@@ -916,6 +943,95 @@ static std::vector<BlobRange> shard_ranges(const void* blob, const kad_batch_hea
   return out;
 }
 
+// Host-side routing of a requirement table (NR requirements, words rq at offsets ro: KAD_B_REQ's encoding)
+// for launch_req_masks, into `out`: BatchDev::req_perm [n_seg_reqs][8], then req_seg [n_seg][4], then req_rows
+// [n_rowreq][8]. K label keys, nch chunks, vr: the snapshot has value rows (SnapDev::vrows).
+// Label requirements whose value ids are all < VR_SLOTS (at most VR_MAX_VALS of them; Exists / DoesNotExist)
+// read the snapshot's value rows (req_row_kernel: a word is the OR of <= 5 row words); so do the label-free
+// ops (TRUE / FALSE / metadata.name =, !=), whose words are constants or one bit. The rest is grouped
+// by label key (req_mask_kernel: one label-row load per segment and chunk): a counting sort by key, cut
+// into segments of <= seg_len ids; shorter segments when the batch has few requirements, so the grid
+// still fills the chip.
+struct ReqRouting {
+  int n_seg = 0, n_rowreq = 0, n_seg_reqs = 0;
+};
+static ReqRouting route_requirements(int NR, const int32_t* ro, const int32_t* rq, int K, size_t nch, bool vr,
+                                     std::vector<int32_t>& out) {
+  int n_seg = 0, n_rowreq = 0;
+  auto by_rows = [&](int r) {
+    const int32_t* q = rq + ro[r];
+    const int op = q[0] & 0xff, n = (int)((uint32_t)q[0] >> 8);
+    // label-free ops: their words need no snapshot data at all
+    if (op == KAD_OP_TRUE || op == KAD_OP_FALSE || op == KAD_OP_NAME_EQ || op == KAD_OP_NAME_NE) return true;
+    if (!vr) return false;
+    if (op == KAD_OP_EXISTS || op == KAD_OP_DNE) return true;
+    if (op != KAD_OP_IN && op != KAD_OP_NOTIN && op != KAD_OP_EQ) return false;
+    if (n > VR_MAX_VALS) return false;
+    for (int t = 0; t < n; t++)
+      if (q[2 + t] < 0 || q[2 + t] >= VR_SLOTS) return false;
+    return true;
+  };
+  // the segment path sees label requirements only (by_rows takes every label-free op): group = label key
+  auto group = [&](int r) { return rq[ro[r] + 1]; };
+  std::vector<uint8_t> rowr((size_t)NR);
+  std::vector<int32_t> start((size_t)K + 2, 0);
+  host_parallel(NR, [&](int lo, int hi) {
+    for (int r = lo; r < hi; r++) rowr[r] = by_rows(r);
+  });
+  for (int r = 0; r < NR; r++) {
+    if (rowr[r])
+      n_rowreq++;
+    else
+      start[(size_t)group(r) + 1]++;
+  }
+  const int NS = NR - n_rowreq;  // requirements on the segment path
+  for (int g = 0; g <= K; g++) start[(size_t)g + 1] += start[g];
+  const long ngrp = ((long)nch + REQ_SEG_G - 1) / REQ_SEG_G;
+  int seg_len = 64;
+  while (seg_len > 8 && (long)NS * ngrp / seg_len < 16384) seg_len /= 2;
+  long segs = 0;
+  for (int g = 0; g <= K; g++) segs += (start[(size_t)g + 1] - start[g] + seg_len - 1) / seg_len;
+  // entry e of req_perm: 8 words (id, word offset, op | n << 8, key word, payload 0..3) so a lane
+  // fetches its requirement with two 16-B loads, independent of the segment's label-row loads;
+  // value-row entries: (id, op | n << 8, key, value ids 0..4)
+  const size_t perm_len = (size_t)NS * 8, seg_len_w = 4 * (size_t)segs;
+  out.assign(perm_len + seg_len_w + (size_t)n_rowreq * 8, 0);
+  std::vector<int32_t> fill(start.begin(), start.end() - 1);
+  int32_t* rows_e = out.data() + perm_len + seg_len_w;
+  int nr2 = 0;
+  for (int r = 0; r < NR; r++) {
+    const int32_t* q = rq + ro[r];
+    const int n = (int)((uint32_t)q[0] >> 8);
+    if (rowr[r]) {
+      int32_t* e = rows_e + 8 * (size_t)nr2++;
+      e[0] = r;
+      e[1] = q[0];
+      e[2] = q[1];
+      for (int t = 0; t < VR_MAX_VALS && t < n; t++) e[3 + t] = q[2 + t];
+      continue;
+    }
+    int32_t* e = out.data() + 8 * (size_t)fill[(size_t)group(r)]++;
+    e[0] = r;
+    e[1] = ro[r];
+    e[2] = q[0];
+    e[3] = q[1];
+    for (int t = 0; t < 4 && t < n; t++) e[4 + t] = q[2 + t];
+  }
+  int32_t* sg = out.data() + perm_len;
+  for (int g = 0; g <= K; g++)
+    for (int f = start[g]; f < start[(size_t)g + 1]; f += seg_len) {
+      sg[4 * n_seg] = g;
+      sg[4 * n_seg + 1] = f;
+      sg[4 * n_seg + 2] = start[(size_t)g + 1] - f < seg_len ? start[(size_t)g + 1] - f : seg_len;
+      n_seg++;
+    }
+  ReqRouting rr;
+  rr.n_seg = n_seg;
+  rr.n_rowreq = n_rowreq;
+  rr.n_seg_reqs = NS;
+  return rr;
+}
+
 // lo, hi: the units this ctx schedules (hi < 0: all); a shard copies only the blob bytes it reads
 // (shard_ranges) into a device buffer of the whole blob's layout, so every offset stays valid. validated:
 // the caller (kad_group_batch_upload) has run validate_batch on this blob already.
@@ -1071,89 +1187,17 @@ static int batch_upload_locked(kad_ctx* c, const void* blob, size_t nbytes, int6
   }
   const size_t nch = (size_t)((c->sd.C + 63) / 64);
   if (int r = grow(c, (void**)&c->d_req_mask, &c->req_mask_cap, (size_t)h.n_reqs * nch * 8)) return r;
-  // Label requirements whose value ids are all < VR_SLOTS (at most VR_MAX_VALS of them; Exists / DoesNotExist)
-  // read the snapshot's value rows (req_row_kernel: a word is the OR of <= 5 row words); so do the label-free
-  // ops (TRUE / FALSE / metadata.name =, !=), whose words are constants or one bit. The rest is grouped
-  // by label key (req_mask_kernel: one label-row load per segment and chunk): a counting sort by key, cut
-  // into segments of <= seg_len ids; shorter segments when the batch has few requirements, so the grid
-  // still fills the chip.
   int n_seg = 0, n_rowreq = 0;
   {
-    const int NR = h.n_reqs, K = c->snap_hdr.n_label_keys;
-    const int32_t* ro = at<int32_t>(blob, h.off, KAD_B_REQ_OFF);
-    const int32_t* rq = at<int32_t>(blob, h.off, KAD_B_REQ);
-    const bool vr = c->sd.vrows != nullptr;
-    auto by_rows = [&](int r) {
-      const int32_t* q = rq + ro[r];
-      const int op = q[0] & 0xff, n = (int)((uint32_t)q[0] >> 8);
-      // label-free ops: their words need no snapshot data at all
-      if (op == KAD_OP_TRUE || op == KAD_OP_FALSE || op == KAD_OP_NAME_EQ || op == KAD_OP_NAME_NE) return true;
-      if (!vr) return false;
-      if (op == KAD_OP_EXISTS || op == KAD_OP_DNE) return true;
-      if (op != KAD_OP_IN && op != KAD_OP_NOTIN && op != KAD_OP_EQ) return false;
-      if (n > VR_MAX_VALS) return false;
-      for (int t = 0; t < n; t++)
-        if (q[2 + t] < 0 || q[2 + t] >= VR_SLOTS) return false;
-      return true;
-    };
-    // the segment path sees label requirements only (by_rows takes every label-free op): group = label key
-    auto group = [&](int r) { return rq[ro[r] + 1]; };
-    std::vector<uint8_t> rowr((size_t)NR);
-    std::vector<int32_t> start((size_t)K + 2, 0);
-    host_parallel(NR, [&](int lo, int hi) {
-      for (int r = lo; r < hi; r++) rowr[r] = by_rows(r);
-    });
-    for (int r = 0; r < NR; r++) {
-      if (rowr[r])
-        n_rowreq++;
-      else
-        start[(size_t)group(r) + 1]++;
-    }
-    const int NS = NR - n_rowreq;  // requirements on the segment path
-    for (int g = 0; g <= K; g++) start[(size_t)g + 1] += start[g];
-    const long ngrp = ((long)nch + REQ_SEG_G - 1) / REQ_SEG_G;
-    int seg_len = 64;
-    while (seg_len > 8 && (long)NS * ngrp / seg_len < 16384) seg_len /= 2;
-    long segs = 0;
-    for (int g = 0; g <= K; g++) segs += (start[(size_t)g + 1] - start[g] + seg_len - 1) / seg_len;
-    // entry e of req_perm: 8 words (id, word offset, op | n << 8, key word, payload 0..3) so a lane
-    // fetches its requirement with two 16-B loads, independent of the segment's label-row loads;
-    // value-row entries: (id, op | n << 8, key, value ids 0..4)
-    const size_t perm_len = (size_t)NS * 8, seg_len_w = 4 * (size_t)segs;
-    c->h_reqseg.assign(perm_len + seg_len_w + (size_t)n_rowreq * 8, 0);
-    std::vector<int32_t> fill(start.begin(), start.end() - 1);
-    int32_t* rows_e = c->h_reqseg.data() + perm_len + seg_len_w;
-    int nr2 = 0;
-    for (int r = 0; r < NR; r++) {
-      const int32_t* q = rq + ro[r];
-      const int n = (int)((uint32_t)q[0] >> 8);
-      if (rowr[r]) {
-        int32_t* e = rows_e + 8 * (size_t)nr2++;
-        e[0] = r;
-        e[1] = q[0];
-        e[2] = q[1];
-        for (int t = 0; t < VR_MAX_VALS && t < n; t++) e[3 + t] = q[2 + t];
-        continue;
-      }
-      int32_t* e = c->h_reqseg.data() + 8 * (size_t)fill[(size_t)group(r)]++;
-      e[0] = r;
-      e[1] = ro[r];
-      e[2] = q[0];
-      e[3] = q[1];
-      for (int t = 0; t < 4 && t < n; t++) e[4 + t] = q[2 + t];
-    }
-    int32_t* sg = c->h_reqseg.data() + perm_len;
-    for (int g = 0; g <= K; g++)
-      for (int f = start[g]; f < start[(size_t)g + 1]; f += seg_len) {
-        sg[4 * n_seg] = g;
-        sg[4 * n_seg + 1] = f;
-        sg[4 * n_seg + 2] = start[(size_t)g + 1] - f < seg_len ? start[(size_t)g + 1] - f : seg_len;
-        n_seg++;
-      }
+    const ReqRouting rr = route_requirements(h.n_reqs, at<int32_t>(blob, h.off, KAD_B_REQ_OFF),
+                                             at<int32_t>(blob, h.off, KAD_B_REQ), c->snap_hdr.n_label_keys, nch,
+                                             c->sd.vrows != nullptr, c->h_reqseg);
+    n_seg = rr.n_seg;
+    n_rowreq = rr.n_rowreq;
     if (int r = grow(c, &c->d_reqseg, &c->reqseg_cap, c->h_reqseg.size() * 4 + 16)) return r;
     if (!c->h_reqseg.empty())
       HIPCHK(c, hipMemcpyAsync(c->d_reqseg, c->h_reqseg.data(), c->h_reqseg.size() * 4, hipMemcpyHostToDevice, c->stream));
-    c->n_seg_reqs = NS;
+    c->n_seg_reqs = rr.n_seg_reqs;
   }
 
   lap("segments");
@@ -1169,6 +1213,11 @@ static int batch_upload_locked(kad_ctx* c, const void* blob, size_t nbytes, int6
   c->unit_n = W;
   c->slot_lo = slot_lo;
   c->slot_n = S;
+  {
+    const int32_t* co = at<int32_t>(blob, h.off, KAD_B_CUR_OFF);
+    c->cur_lo = co[lo];
+    c->cur_n = co[hi] - co[lo];
+  }
   const char* base = static_cast<const char*>(c->d_batch);
   BatchDev& b = c->bd;
   b.W = W;
@@ -1716,6 +1765,301 @@ int kad_explain_timing(kad_ctx* c, float ms[2]) {
   HIPCHK(c, hipEventSynchronize(c->xev[2]));
   HIPCHK(c, hipEventElapsedTime(&ms[0], c->xev[0], c->xev[1]));
   HIPCHK(c, hipEventElapsedTime(&ms[1], c->xev[1], c->xev[2]));
+  return KAD_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------ override policies
+// A policy-set blob may come from any packer: before it is copied to the device every array is checked to
+// lie in the blob, every CSR offset array to be monotone, every id the kernels index with to be in range
+// and every target program to be well formed. Host only: sh is the header of the snapshot it was packed for.
+static int validate_policies(const void* blob, size_t nbytes, const kad_snapshot_header& sh, kad_override_header* hdr,
+                             std::string* err) {
+  auto bad = [&](const std::string& m) {
+    *err = m;
+    return KAD_EINVAL;
+  };
+  kad_override_header h;
+  if (!blob || nbytes < sizeof(h)) return bad("policy set too small");
+  std::memcpy(&h, blob, sizeof(h));
+  if (h.magic != KAD_OVERRIDE_MAGIC) return bad("bad policy set magic");
+  if (h.abi_version != KAD_ABI_VERSION) return bad("policy set ABI version mismatch");
+  if (h.total_bytes != nbytes) return bad("policy set size mismatch");
+  if (h.snapshot_fingerprint != sh.fingerprint || h.n_clusters != sh.n_clusters)
+    return bad("policy set was packed against a different snapshot");
+  const int P = h.n_policies, R = h.n_rules, NR = h.n_reqs, C = sh.n_clusters, K = sh.n_label_keys;
+  if (P < 0 || R < 0 || NR < 0) return bad("bad policy set counts");
+  const char* base = static_cast<const char*>(blob);
+  auto extent = [&](int a, uint64_t count) {
+    const uint64_t o = h.off[a];
+    return o <= nbytes && !(o & 7) && count <= (nbytes - o) / 4;
+  };
+  auto arr = [&](int a) { return reinterpret_cast<const int32_t*>(base + h.off[a]); };
+  // offsets off_a[0 .. n]: from 0, non-decreasing; the data array holds off[n] words
+  auto csr = [&](int off_a, int n, int data_a) {
+    if (!extent(off_a, (uint64_t)n + 1)) return false;
+    const int32_t* o = arr(off_a);
+    if (o[0] != 0) return false;
+    for (int i = 0; i < n; i++)
+      if (o[i + 1] < o[i]) return false;
+    return data_a < 0 || extent(data_a, (uint64_t)o[n]);
+  };
+  if (!csr(KAD_O_POL_RULE_OFF, P, -1) || arr(KAD_O_POL_RULE_OFF)[P] != R)
+    return bad("policy rule offsets must run from 0 to n_rules");
+  if (!extent(KAD_O_RULE_FLAGS, (uint64_t)R)) return bad("policy set array rule_flags lies outside the blob");
+  if (!csr(KAD_O_RULE_NAME_OFF, R, KAD_O_RULE_NAME)) return bad("bad rule name offsets");
+  if (!csr(KAD_O_RULE_PROG_OFF, R, KAD_O_RULE_PROG)) return bad("bad rule program offsets");
+  if (!csr(KAD_O_REQ_OFF, NR, KAD_O_REQ)) return bad("bad requirement offsets");
+  const uint32_t* fl = reinterpret_cast<const uint32_t*>(arr(KAD_O_RULE_FLAGS));
+  const int32_t *no = arr(KAD_O_RULE_NAME_OFF), *nm = arr(KAD_O_RULE_NAME);
+  const int32_t *po = arr(KAD_O_RULE_PROG_OFF), *pg = arr(KAD_O_RULE_PROG);
+  const int32_t *ro = arr(KAD_O_REQ_OFF), *rq = arr(KAD_O_REQ);
+  for (int r = 0; r < NR; r++) {  // [op | n << 8, key, payload...], as validate_batch
+    const int len = ro[r + 1] - ro[r];
+    if (len < 2) return bad("requirement shorter than two words");
+    const int32_t* p = rq + ro[r];
+    const int op = p[0] & 0xff, n = (int)((uint32_t)p[0] >> 8), key = p[1];
+    if (len != 2 + n) return bad("requirement payload length mismatch");
+    const bool label_key = key >= 0 && key < K;
+    bool ok;
+    switch (op) {
+      case KAD_OP_IN: case KAD_OP_NOTIN: case KAD_OP_EQ: ok = label_key && n >= 1; break;
+      case KAD_OP_EXISTS: case KAD_OP_DNE: ok = label_key && n == 0; break;
+      case KAD_OP_GT: case KAD_OP_LT: ok = label_key && n == 2; break;
+      case KAD_OP_NAME_EQ: case KAD_OP_NAME_NE: ok = key >= -1 && key < C; break;
+      case KAD_OP_TRUE: case KAD_OP_FALSE: ok = true; break;
+      default: ok = false;
+    }
+    if (!ok) return bad("bad requirement " + std::to_string(r));
+  }
+  for (int r = 0; r < R; r++) {
+    if (fl[r] & ~(KAD_OVR_HAS_TARGET | KAD_OVR_HAS_NAMES | KAD_OVR_SEL_INVALID | KAD_OVR_BAD_VALUE))
+      return bad("unknown flags of rule " + std::to_string(r));
+    for (int j = no[r]; j < no[r + 1]; j++)
+      if (nm[j] < 0 || nm[j] >= C || (j > no[r] && nm[j] <= nm[j - 1]))
+        return bad("cluster ids of rule " + std::to_string(r) + " must be ascending snapshot ids");
+    // the program: every requirement id in range, the structure consumes exactly the rule's words
+    const int32_t* p = pg + po[r];
+    const int64_t len = po[r + 1] - po[r];
+    auto ids_ok = [&](int64_t at, int64_t n) {
+      if (n < 0 || at + n > len) return false;
+      for (int64_t i = 0; i < n; i++)
+        if (p[at + i] < 0 || p[at + i] >= NR) return false;
+      return true;
+    };
+    bool ok = len >= 2;
+    int64_t pc = 0;
+    if (ok) {
+      const int64_t n_sel = p[pc++];
+      ok = ids_ok(pc, n_sel);
+      pc += ok ? n_sel : 0;
+      ok = ok && pc < len;
+      if (ok && p[pc++]) {
+        ok = pc < len;
+        const int64_t n_terms = ok ? p[pc++] : 0;
+        ok = ok && n_terms >= 0;
+        for (int64_t t = 0; ok && t < n_terms; t++) {
+          ok = pc + 3 <= len;
+          if (!ok) break;
+          const int64_t ne = p[pc + 1], nf = p[pc + 2];
+          ok = ne >= 0 && nf >= 0 && ids_ok(pc + 3, ne + nf);
+          pc += 3 + (ok ? ne + nf : 0);
+        }
+      }
+    }
+    if (!ok || pc != len) return bad("malformed target program of rule " + std::to_string(r));
+  }
+  *hdr = h;
+  return KAD_OK;
+}
+
+static int override_policies_upload_locked(kad_ctx* c, const void* blob, size_t nbytes) {
+  c->have_ovr = false;  // a failed upload leaves no policy set resident
+  if (!c->have_snapshot) return fail(c, KAD_ESTATE, "no snapshot uploaded");
+  kad_override_header h;
+  std::string err;
+  if (int r = validate_policies(blob, nbytes, c->snap_hdr, &h, &err)) return fail(c, r, err);
+  HIPCHK(c, hipSetDevice(c->device));
+  if (int r = grow(c, &c->d_ovr, &c->ovr_cap, nbytes)) return r;
+  HIPCHK(c, hipMemcpyAsync(c->d_ovr, blob, nbytes, hipMemcpyHostToDevice, c->stream));
+  const int32_t* pro = at<int32_t>(blob, h.off, KAD_O_POL_RULE_OFF);
+  c->h_ovr_pro.assign(pro, pro + h.n_policies + 1);
+  const size_t nch = (size_t)((c->sd.C + 63) / 64);
+  const ReqRouting rr = route_requirements(h.n_reqs, at<int32_t>(blob, h.off, KAD_O_REQ_OFF),
+                                           at<int32_t>(blob, h.off, KAD_O_REQ), c->snap_hdr.n_label_keys, nch,
+                                           c->sd.vrows != nullptr, c->h_ovr_reqseg);
+  c->ovr_n_seg = rr.n_seg;
+  c->ovr_n_rowreq = rr.n_rowreq;
+  c->ovr_n_seg_reqs = rr.n_seg_reqs;
+  if (int r = grow(c, &c->d_ovr_reqseg, &c->ovr_reqseg_cap, c->h_ovr_reqseg.size() * 4 + 16)) return r;
+  if (!c->h_ovr_reqseg.empty())
+    HIPCHK(c, hipMemcpyAsync(c->d_ovr_reqseg, c->h_ovr_reqseg.data(), c->h_ovr_reqseg.size() * 4, hipMemcpyHostToDevice,
+                             c->stream));
+  if (int r = grow(c, &c->d_ovr_rows, &c->ovr_rows_cap, ((size_t)h.n_reqs + 2 * (size_t)h.n_rules) * nch * 8)) return r;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->ovr_hdr = h;
+  c->have_ovr = true;
+  return KAD_OK;
+}
+
+static int override_match_locked(kad_ctx* c, const kad_override_batch* b, const kad_override_view* out) {
+  if (!c->have_snapshot || !c->have_ovr) return fail(c, KAD_ESTATE, "snapshot and policy set must be uploaded first");
+  const bool from_results = b->place_off == nullptr;
+  if (from_results && (!c->have_batch || !c->ran)) return fail(c, KAD_ESTATE, "nothing has been scheduled");
+  const kad_override_header& h = c->ovr_hdr;
+  const int n = b->n_objects, RW = b->rule_words, P = h.n_policies, C = c->sd.C;
+  if (n < 0 || RW < 1 || (n && (!b->obj_policy || !out || !out->status)))
+    return fail(c, KAD_EINVAL, "object list or output view missing");
+  if (from_results && n != c->bd.W) return fail(c, KAD_EINVAL, "n_objects differs from the resident batch's units");
+  if (!from_results && (b->place_off[0] != 0 || (b->place_off[n] && !b->place_cluster)))
+    return fail(c, KAD_EINVAL, "place_off must start at 0");
+  const int32_t* pro = c->h_ovr_pro.data();
+  {
+    const int32_t* op = b->obj_policy;
+    const int64_t i = first_bad(n, [&](int64_t i) {
+      int64_t rules = 0;
+      for (int q = 0; q < 2; q++) {
+        const int p = op[2 * i + q];
+        if (p < -1 || p >= P) return true;
+        if (p >= 0) rules += pro[p + 1] - pro[p];
+      }
+      return rules > 32 * (int64_t)RW;
+    });
+    if (i >= 0)
+      return fail(c, KAD_EINVAL, "object " + std::to_string(i) + ": policy index out of range, or more than 32 * rule_words rules");
+  }
+  int64_t n_slots;
+  if (from_results) {
+    n_slots = c->slot_n + c->cur_n;
+  } else {
+    const int32_t* po = b->place_off;
+    if (first_bad(n, [&](int64_t i) { return po[i + 1] < po[i]; }) >= 0)
+      return fail(c, KAD_EINVAL, "place_off must be non-decreasing");
+    n_slots = po[n];
+    const int32_t* pc = b->place_cluster;
+    if (first_bad(n_slots, [&](int64_t j) { return pc[j] < -1 || pc[j] >= C; }) >= 0)
+      return fail(c, KAD_EINVAL, "placed cluster id out of range");
+  }
+  if (n == 0) return KAD_OK;
+  if (n_slots && !out->matched) return fail(c, KAD_EINVAL, "output view missing");
+  HIPCHK(c, hipSetDevice(c->device));
+  // one buffer: obj_policy, place_off, place_cluster, then status and the matched rows
+  auto a256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t o_po = a256(8 * (size_t)n);
+  const size_t o_pc = o_po + (from_results ? 0 : a256(4 * ((size_t)n + 1)));
+  const size_t o_st = o_pc + (from_results ? 0 : a256(4 * (size_t)n_slots));
+  const size_t o_m = o_st + a256(4 * (size_t)n);
+  const size_t m_bytes = 4 * (size_t)n_slots * RW;
+  if (int r = grow(c, &c->d_ovr_work, &c->ovr_work_cap, o_m + m_bytes)) return r;
+  char* d = static_cast<char*>(c->d_ovr_work);
+  HIPCHK(c, hipMemcpyAsync(d, b->obj_policy, 8 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+  if (!from_results) {
+    HIPCHK(c, hipMemcpyAsync(d + o_po, b->place_off, 4 * ((size_t)n + 1), hipMemcpyHostToDevice, c->stream));
+    if (n_slots) HIPCHK(c, hipMemcpyAsync(d + o_pc, b->place_cluster, 4 * (size_t)n_slots, hipMemcpyHostToDevice, c->stream));
+  }
+  const size_t nch = (size_t)((C + 63) / 64);
+  const char* base = static_cast<const char*>(c->d_ovr);
+  uint64_t* rows = static_cast<uint64_t*>(c->d_ovr_rows);
+  // requirement rows of the set's table: req_row_kernel and req_mask_kernel read these fields only
+  BatchDev rb{};
+  rb.NR = h.n_reqs;
+  rb.req_off = at<int32_t>(base, h.off, KAD_O_REQ_OFF);
+  rb.req = at<int32_t>(base, h.off, KAD_O_REQ);
+  rb.req_mask = rows;
+  rb.n_seg = c->ovr_n_seg;
+  rb.req_perm = static_cast<const int32_t*>(c->d_ovr_reqseg);
+  rb.req_seg = reinterpret_cast<const int4*>(rb.req_perm + (size_t)c->ovr_n_seg_reqs * 8);
+  rb.n_rowreq = c->ovr_n_rowreq;
+  rb.req_rows = reinterpret_cast<const int4*>(reinterpret_cast<const int32_t*>(rb.req_seg) + 4 * (size_t)c->ovr_n_seg);
+  OverrideDev o{};
+  o.C = C;
+  o.P = P;
+  o.R = h.n_rules;
+  o.pol_rule_off = at<int32_t>(base, h.off, KAD_O_POL_RULE_OFF);
+  o.rule_flags = at<uint32_t>(base, h.off, KAD_O_RULE_FLAGS);
+  o.name_off = at<int32_t>(base, h.off, KAD_O_RULE_NAME_OFF);
+  o.name = at<int32_t>(base, h.off, KAD_O_RULE_NAME);
+  o.prog_off = at<int32_t>(base, h.off, KAD_O_RULE_PROG_OFF);
+  o.prog = at<int32_t>(base, h.off, KAD_O_RULE_PROG);
+  o.req_mask = rows;
+  o.M = rows + (size_t)h.n_reqs * nch;
+  o.E = o.M + (size_t)h.n_rules * nch;
+  o.n_obj = n;
+  o.RW = RW;
+  o.obj_policy = reinterpret_cast<const int32_t*>(d);
+  o.from_results = from_results ? 1 : 0;
+  if (from_results) {
+    o.out_off = c->bd.out_off;
+    o.cur_off = c->bd.cur_off;
+    o.cur_id = c->bd.cur_id;
+    o.res_status = c->d_status;
+    o.res_count = c->d_count;
+    o.res_cluster = c->d_cluster;
+    o.slot_lo = c->slot_lo;
+    o.n_out = c->slot_n;
+    o.cur_lo = c->cur_lo;
+  } else {
+    o.place_off = reinterpret_cast<const int32_t*>(d + o_po);
+    o.place_cluster = reinterpret_cast<const int32_t*>(d + o_pc);
+  }
+  o.n_slots = n_slots;
+  o.status = reinterpret_cast<int32_t*>(d + o_st);
+  o.matched = reinterpret_cast<uint32_t*>(d + o_m);
+  HIPCHK(c, hipEventRecord(c->oev[0], c->stream));
+  bool zeroed = false;
+  HIPCHK(c, launch_req_masks(c->sd, rb, c->stream, false, &zeroed));
+  HIPCHK(c, hipEventRecord(c->oev[1], c->stream));
+  HIPCHK(c, launch_override_rule_rows(o, c->stream));
+  HIPCHK(c, hipEventRecord(c->oev[2], c->stream));
+  HIPCHK(c, launch_override_match(o, c->stream));
+  HIPCHK(c, hipEventRecord(c->oev[3], c->stream));
+  c->ovr_ran = true;
+  HIPCHK(c, hipMemcpyAsync(out->status, o.status, 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  if (m_bytes) HIPCHK(c, hipMemcpyAsync(out->matched, o.matched, m_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return KAD_OK;
+}
+
+extern "C" {
+
+// Host only (tests, packers): validate_policies against the header of a packed snapshot blob.
+int kad_override_policies_check(const void* blob, size_t nbytes, const void* snapshot_blob, size_t snapshot_nbytes) {
+  try {
+    kad_snapshot_header sh;
+    if (!snapshot_blob || snapshot_nbytes < sizeof(sh)) return KAD_EINVAL;
+    std::memcpy(&sh, snapshot_blob, sizeof(sh));
+    if (sh.magic != KAD_SNAPSHOT_MAGIC) return KAD_EINVAL;
+    kad_override_header h;
+    std::string err;
+    return validate_policies(blob, nbytes, sh, &h, &err);
+  } catch (...) {
+    return KAD_EHOST;
+  }
+}
+
+int kad_override_policies_upload(kad_ctx* c, const void* blob, size_t nbytes) {
+  return guarded(c, [&]() -> int {
+    if (!c || !blob) return KAD_EINVAL;
+    std::lock_guard<std::mutex> g(c->mu);
+    return override_policies_upload_locked(c, blob, nbytes);
+  });
+}
+
+int kad_override_match(kad_ctx* c, const kad_override_batch* b, const kad_override_view* out) {
+  return guarded(c, [&]() -> int {
+    if (!c || !b) return KAD_EINVAL;
+    std::lock_guard<std::mutex> g(c->mu);
+    return override_match_locked(c, b, out);
+  });
+}
+
+int kad_override_timing(kad_ctx* c, float ms[3]) {
+  if (!c || !ms) return KAD_EINVAL;
+  std::lock_guard<std::mutex> g(c->mu);
+  if (!c->ovr_ran) return fail(c, KAD_ESTATE, "no kad_override_match ran");
+  HIPCHK(c, hipEventSynchronize(c->oev[3]));
+  for (int i = 0; i < 3; i++) HIPCHK(c, hipEventElapsedTime(&ms[i], c->oev[i], c->oev[i + 1]));
   return KAD_OK;
 }
 

@@ -302,6 +302,35 @@ struct ExplainArgs {
 };
 hipError_t launch_explain(const ExplainArgs& a, hipStream_t st);
 
+// kad_override_match (kad_override.hip): the resident policy set, its rows and one batch of objects.
+struct OverrideDev {
+  int C, P, R;
+  const int32_t* pol_rule_off;   // [P + 1]
+  const uint32_t* rule_flags;    // [R] KAD_OVR_*
+  const int32_t *name_off, *name, *prog_off, *prog;
+  const uint64_t* req_mask;      // [NR][nch] the set's requirement rows
+  uint64_t *M, *E;               // [R][nch] rule × cluster rows: matches, errors (override_rule_rows_kernel)
+  // the batch
+  int n_obj, RW;
+  const int32_t* obj_policy;     // [n_obj][2]
+  // explicit placements (from_results == 0): slots [place_off[i], place_off[i + 1]) of place_cluster
+  const int32_t *place_off, *place_cluster;
+  // the last schedule's results (from_results == 1): slot s < n_out is output slot s + slot_lo of unit i's
+  // range when s - (out_off[i] - slot_lo) < count[i] and status[i] == KAD_ST_OK; slot n_out + j is entry
+  // j + cur_lo of KAD_B_CUR_ID, placed when its unit's status is KAD_ST_STICKY
+  int from_results;
+  const int64_t* out_off;        // [n_obj + 1] (BatchDev::out_off)
+  const int32_t* cur_off;        // [n_obj + 1] (BatchDev::cur_off)
+  const int32_t *res_status, *res_count, *res_cluster, *cur_id;
+  int64_t slot_lo, n_out;
+  int32_t cur_lo;
+  int64_t n_slots;
+  int32_t* status;               // [n_obj]
+  uint32_t* matched;             // [n_slots][RW]
+};
+hipError_t launch_override_rule_rows(const OverrideDev& o, hipStream_t st);
+hipError_t launch_override_match(const OverrideDev& o, hipStream_t st);
+
 // kad_snapshot_update: scatter the changed clusters' columns of every snapshot
 // array from a resident delta blob into the resident snapshot blob.
 struct DeltaDev {

@@ -19,6 +19,7 @@ import numpy as np
 
 from . import types as T
 from .framework import Framework
+from . import pack as _pack
 from .pack import Batch, Snapshot, SnapshotDelta
 from .results import BatchResult, FilterDiagnosis, to_schedule_result
 
@@ -50,6 +51,15 @@ class ResultState(ctypes.Structure):  # kad_result_state
     _fields_ = [("n_units", ctypes.c_int32), ("place_off", ctypes.c_void_p), ("place_cluster", ctypes.c_void_p),
                 ("place_has", ctypes.c_void_p), ("ovr_off", ctypes.c_void_p), ("ovr_cluster", ctypes.c_void_p),
                 ("ovr_value", ctypes.c_void_p), ("ovr_kind", ctypes.c_void_p)]
+
+
+class OverrideBatch(ctypes.Structure):  # kad_override_batch
+    _fields_ = [("n_objects", ctypes.c_int32), ("rule_words", ctypes.c_int32), ("obj_policy", ctypes.c_void_p),
+                ("place_off", ctypes.c_void_p), ("place_cluster", ctypes.c_void_p)]
+
+
+class OverrideView(ctypes.Structure):  # kad_override_view
+    _fields_ = [("status", ctypes.c_void_p), ("matched", ctypes.c_void_p)]
 
 
 _lib = None
@@ -102,6 +112,11 @@ def load_library(path: str = LIB_PATH):
     if hasattr(L, "kad_explain"):  # (absent from libraries of older revisions: A/B runs)
         L.kad_explain.argtypes = [P, P, P, I, P, I, P]
         L.kad_explain_timing.argtypes = [P, P]
+    if hasattr(L, "kad_override_match"):  # (absent from libraries of older revisions: A/B runs)
+        L.kad_override_policies_upload.argtypes = [P, P, SZ]
+        L.kad_override_policies_check.argtypes = [P, SZ, P, SZ]
+        L.kad_override_match.argtypes = [P, P, P]
+        L.kad_override_timing.argtypes = [P, P]
     L.kad_debug_inject_fault.argtypes = [P, I]
     L.kad_debug_plan_force_workspace.argtypes = [P, I]
     L.kad_trigger_suffix_upload.argtypes = [P, P, SZ]
@@ -369,6 +384,43 @@ class Context:
         ms = (ctypes.c_float * 2)()
         self._chk(self.L.kad_explain_timing(self.h, ms))
         return float(ms[0]), float(ms[1])
+
+    def upload_override_policies(self, policy_set):
+        """kad_override_policies_upload: an overrides.PolicySet packed against the uploaded snapshot."""
+        self._chk(self.L.kad_override_policies_upload(self.h, _p(policy_set.blob), policy_set.blob.nbytes))
+        self.policy_set = policy_set
+
+    def override_match(self, obj_policy, placed=None, rule_words: Optional[int] = None):
+        """kad_override_match → (status[n], matched[n_slots][RW]). ``obj_policy``: [n][2] indices into the
+        uploaded policy set (-1: none; column 0 the ClusterOverridePolicy). ``placed``: (place_off[n + 1],
+        place_cluster[]) as snapshot cluster ids, or None for the placements of the last schedule(): the
+        slots are then the batch's output slots followed by its CurrentClusters entries (sticky units)."""
+        op = np.ascontiguousarray(obj_policy, np.int32).reshape(-1, 2)
+        n = len(op)
+        rw = rule_words if rule_words is not None else self.policy_set.rule_words(op)
+        if placed is None:
+            hdr = _pack.header_of(self.batch.blob, _pack.BatchHeader)
+            cur_off = _pack.array_of(self.batch.blob, hdr, _pack.B_CUR_OFF, np.int32, hdr.n_units + 1)
+            n_slots = int(hdr.n_out_slots) + int(cur_off[hdr.n_units])
+            off = ids = None
+        else:
+            off = np.ascontiguousarray(placed[0], np.int32)
+            ids = np.ascontiguousarray(placed[1], np.int32)
+            n_slots = len(ids)
+        status = np.zeros(max(1, n), np.int32)
+        matched = np.zeros((max(1, n_slots), rw), np.uint32)
+        b = OverrideBatch(n, rw, op.ctypes.data, None if off is None else off.ctypes.data,
+                          None if ids is None or not len(ids) else ids.ctypes.data)
+        v = OverrideView(status.ctypes.data, matched.ctypes.data)
+        self._chk(self.L.kad_override_match(self.h, ctypes.byref(b), ctypes.byref(v)))
+        return status[:n], matched[:n_slots]
+
+    def override_timing(self):
+        """kad_override_timing: device ms of the last override_match() — (the policy set's requirement rows,
+        override_rule_rows_kernel, the status + match kernels)."""
+        ms = (ctypes.c_float * 3)()
+        self._chk(self.L.kad_override_timing(self.h, ms))
+        return float(ms[0]), float(ms[1]), float(ms[2])
 
     def select_rows(self, rows: Sequence[Sequence[int]], max_clusters: Sequence[Optional[int]], flags: int = 0):
         """MaxCluster on explicit score rows → per row (status, sorted selected positions)."""

@@ -997,3 +997,52 @@ def gen_result_objects(rng: np.random.Generator, W: int, names: List[str], repli
             obj["spec"]["overrides"] = ovs
         out.append(obj)
     return out
+
+
+def gen_override_policies(seed: int, clusters, n_policies: int = 40, max_rules: int = 6, n_keys: int = 4,
+                          n_vals: int = 3, n_int_keys: int = 2, p_invalid: float = 0.03, namespaces=("ns",)):
+    """(Cluster)OverridePolicies over the label vocabulary of :func:`gen_clusters` / :func:`gen_fuzz` clusters:
+    0..max_rules rules each, targets mixing nil, names (some unknown), selectors, affinity terms with fields and
+    empty terms, and — with probability ``p_invalid`` per part — invalid selectors, expressions, fields and
+    patch values. Draws from its own generator, so no other seeded workload changes."""
+    from . import overrides as OV
+
+    rng = np.random.default_rng([seed, 0x6F7672])
+    r = rng.random
+    names = [c.name for c in clusters] + ["ghost-cluster"]
+    values = [b"1", b'"s"', b'{"k": [1, true, null]}', b"[1.5, 2]", b""]
+    pols = []
+    for i in range(n_policies):
+        rules = []
+        for _ in range(int(rng.integers(0, max_rules + 1))):
+            tc = None
+            if r() < 0.85:
+                tc = OV.TargetClusters()
+                if r() < 0.35:
+                    k = int(rng.integers(0, min(len(names), 8) + 1))
+                    tc.clusters = [names[int(j)] for j in rng.integers(0, len(names), k)]
+                if r() < 0.35:
+                    tc.cluster_selector = {f"key{int(rng.integers(0, n_keys))}": f"val{int(rng.integers(0, n_vals))}"
+                                           for _ in range(int(rng.integers(0, 3)))}
+                    if r() < p_invalid:
+                        tc.cluster_selector["bad key/with/slashes" if r() < 0.5 else "key0"] = "invalid value: @"
+                if r() < 0.5:
+                    terms = []
+                    for _ in range(int(rng.integers(0, 4))):
+                        exprs = [_expr(rng, n_keys, n_vals, n_int_keys, all_ops=True, p_invalid=p_invalid)
+                                 for _ in range(int(rng.integers(0, 3)))]
+                        fields = None
+                        if r() < 0.3:
+                            op = T.OP_EXISTS if r() < p_invalid else (T.OP_IN if r() < 0.6 else T.OP_NOT_IN)
+                            fields = [T.ClusterSelectorRequirement("metadata.name", op,
+                                                                   [names[int(rng.integers(0, len(names)))]])]
+                        terms.append(T.ClusterSelectorTerm(exprs or None, fields))
+                    tc.cluster_affinity = terms
+            patches = [OV.JsonPatchOverrider(["add", "replace", "remove"][int(rng.integers(0, 3))],
+                                             f"/spec/f{int(rng.integers(0, 6))}",
+                                             b"{broken" if r() < p_invalid else values[int(rng.integers(0, len(values)))])
+                       for _ in range(int(rng.integers(0, 3)))]
+            rules.append(OV.OverrideRule(tc, patches))
+        ns = None if i % 2 == 0 else namespaces[int(rng.integers(0, len(namespaces)))]
+        pols.append(OV.OverridePolicy(f"op-{seed}-{i}", ns, rules))
+    return pols
