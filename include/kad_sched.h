@@ -359,6 +359,33 @@ int kad_path_counts(kad_ctx* ctx, int32_t* out);
  * folded into the static words, [4] the fit threshold rows folded too. Returns KAD_ESTATE without a
  * snapshot. Measurement / tests only. No reference counterpart. */
 int kad_snapshot_paths(kad_ctx* ctx, int32_t* out);
+/* The kernels a kad_schedule launches and their shapes, as the library's route decision computes them (csrc/
+ * kad_route.h route_schedule). No device work and no ctx: in[KAD_ROUTE_IN_FIELDS] is
+ *   [0] C, [1] exact-f64 path (kad_snapshot_paths out[1]), [2] fold, [3] fitfold, [4] taint words TW,
+ *   [5] some cpu / memory amount < 0 or >= 2^46,
+ *   [6] W, [7] some unit has CurrentClusters, [8] no unit has a ResourceRequest, [9] some unit uses a feature
+ *   the lean kernel defers, [10] some unit has more than 8 preferred terms,
+ *   [11] filter_mask, [12] score_mask,
+ *   [13] debug capture requested (kad_debug_scores), [14] a side stream exists, [15] compute units,
+ *   [16] KAD_NO_ROWS (0), [17] KAD_ROWS_AFTER (0), [18] KAD_ROWS_NO_INLINE (0), [19] KAD_PREP_WAVE (1),
+ *   [20] KAD_WIDE_MIN_NCH (5), [21] KAD_LEAN_BLOCKS_PER_CU (0: the occupancy query's answer) — the tuning
+ *   variables of measurement builds, with the defaults every product build runs;
+ * per_cu / row_per_cu stand for the occupancy queries of the main and the row kernel. out[KAD_ROUTE_FIELDS] is
+ *   [0] prep kernel (0 prep_kernel, 1..3 prep_wave_kernel<2..4>),
+ *   [1] prep_kernel lanes per unit, [2] family (0 lean, 1 wide), [3] the main kernel's variant
+ *   (kad_route_variant_name), [4] the row kernel's, [5] the defer pass's, [6] use_rows, [7] early_rows,
+ *   [8] may_defer, [9] row kernel placement (0 none, 1 inside the wide kernel, 2 beside it, 3 after the main
+ *   kernel), [10] 1 if the defer pass runs, [11] cache_ne, [12] cache_pn, [13] cache_zs, [14] waves per block,
+ *   [15] block threads, [16] dynamic LDS bytes, [17] of them per wave, [18] grid, [19] work-queue batch size,
+ *   [20] the row kernel's grid (0 unless placement 2 or 3); [18..20] are 0 at W = 0 (prep alone runs then).
+ * [15] compute units is the count of the first device the process scheduled on, whichever device ctx is on.
+ * kad_last_route: the same record for what the last kad_schedule launched (KAD_ESTATE before one).
+ * Measurement / tests only. No reference counterpart. */
+#define KAD_ROUTE_IN_FIELDS 22
+#define KAD_ROUTE_FIELDS 21
+int kad_route_eval(const int32_t* in, int32_t per_cu, int32_t row_per_cu, int32_t* out);
+int kad_last_route(kad_ctx* ctx, int32_t* out);
+const char* kad_route_variant_name(int32_t variant);
 int kad_results_download(kad_ctx* ctx, const kad_result_view* out);
 /* Page-locked host memory for the download's (or a batch blob's) buffers, reused across batches: the
  * copies then DMA straight into / out of it (no staging). kad_host_free(NULL) is a no-op. Caller-side

@@ -122,6 +122,7 @@ struct kad_ctx {
   bool batch_defer = false;    // some unit uses a feature the lean kernel defers
   bool batch_zero_req = false;  // no unit has a ResourceRequest (BatchDev::zero_req)
   bool batch_many_terms = false;  // some unit has more than ROW_MAX_TERMS preferred terms (the row path defers it)
+  Route route{};               // what the last kad_schedule launched (kad_last_route)
   // scheduling-trigger hashes (kad_trigger_*)
   void* t_suffix = nullptr;
   size_t t_suffix_cap = 0;
@@ -1355,23 +1356,17 @@ static int schedule_locked(kad_ctx* c, const kad_profile* p, uint8_t* dbg_feas, 
   o.dbg_feas = dbg_feas;
   o.dbg_total = dbg_total;
   const bool tm = c->timing;
-  // long feasible lists go to schedule_row_kernel when every filter is in the static words
-  const bool no_rows = tuning_env("KAD_NO_ROWS", 0) != 0;  // (read per launch: tuning builds only)
-  c->bd.use_rows = !no_rows && c->sd.clean && c->sd.fold && c->sd.fitfold && row_kernel_fits(c->sd.C);
-  const bool rows_after = tuning_env("KAD_ROWS_AFTER", 0) != 0;
-  const int per = prep_lanes_per_unit(c->sd.C);
-  const bool wide = wide_path(c->sd);
-  c->bd.early_rows = c->bd.use_rows && !rows_after && wide && (per & (per - 1)) == 0 && per <= 64 &&
-                     !dbg_feas && !dbg_total;
-  // can any unit reach the defer list (schedule_kernel)? The wide kernel with early routing (every filter in
-  // the static words, long lists routed by prep) defers only the units batch_defer names; the row path also
-  // those with more preferred terms than it holds. Otherwise as before: the lean kernel's own reasons, and
-  // on the wide path without early routing, lists past WIDE_P.
-  const bool rows_defer = c->batch_many_terms && (p->score_mask & (1u << KAD_PL_CLUSTER_AFFINITY));
-  if (wide)
-    c->bd.may_defer = c->batch_defer || dbg_feas || dbg_total || !c->bd.early_rows || rows_defer;
-  else
-    c->bd.may_defer = c->batch_defer || c->snap_negative || c->sd.TW > 1 || dbg_feas || dbg_total;
+  // which kernels run, and the three flags of it the kernels read: route_schedule (kad_route.h)
+  RouteIn in{c->sd.C, c->sd.clean, c->sd.fold, c->sd.fitfold, c->sd.TW, c->snap_negative,
+             c->bd.W, (c->bd.flags_or & KAD_W_HAS_CURRENT) != 0, c->bd.zero_req, c->batch_defer, c->batch_many_terms,
+             (int32_t)p->filter_mask, (int32_t)p->score_mask,
+             dbg_feas || dbg_total, c->side && c->fork_ev && c->join_ev, n_cus()};
+  route_tuning(in);
+  Route& rt = c->route;
+  rt = route_schedule(in);
+  c->bd.use_rows = rt.use_rows;
+  c->bd.early_rows = rt.early_rows;
+  c->bd.may_defer = rt.may_defer;
   if (c->bd.use_rows) {
     if (int r = grow(c, &c->d_rowslab, &c->rowslab_cap, (size_t)ROW_MAX_BLOCKS * row_slab_bytes(c->sd.C))) return r;
     c->bd.row_slabs = static_cast<char*>(c->d_rowslab);
@@ -1383,13 +1378,12 @@ static int schedule_locked(kad_ctx* c, const kad_profile* p, uint8_t* dbg_feas, 
   HIPCHK(c, launch_req_masks(c->sd, c->bd, c->stream, c->bd.early_rows, &zeroed));
   if (tm) HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
   if (c->bd.early_rows && !zeroed) HIPCHK(c, hipMemsetAsync(c->bd.rows_n, 0, 2 * sizeof(int32_t), c->stream));
-  if (fast_path(c->sd.C))
-    HIPCHK(c, launch_prep(c->sd, c->bd, pd, dbg_feas || dbg_total, c->stream));
+  HIPCHK(c, launch_prep(c->sd, c->bd, pd, dbg_feas || dbg_total, rt, c->stream));
   if (tm) HIPCHK(c, hipEventRecord(c->ev[4], c->stream));
   if (tm) HIPCHK(c, hipEventRecord(c->ev[5], c->stream));  // re-recorded after the main kernel when it runs
   if (tm) HIPCHK(c, hipEventRecord(c->ev[6], c->stream));  // re-recorded after the long-row kernel
-  HIPCHK(c, launch_schedule(c->sd, c->bd, o, pd, c->d_scratch, c->scratch_bytes, c->stream, tm ? c->ev[5] : nullptr,
-                            tm ? c->ev[6] : nullptr, c->side, c->fork_ev, c->join_ev));
+  HIPCHK(c, launch_schedule(c->sd, c->bd, o, pd, in, rt, c->d_scratch, c->scratch_bytes, c->stream,
+                            tm ? c->ev[5] : nullptr, tm ? c->ev[6] : nullptr, c->side, c->fork_ev, c->join_ev));
   if (tm) HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
   if (p->replicas_plugin == KAD_PL_CLUSTER_CAPACITY_WEIGHT && !c->plan_rows.empty())
     HIPCHK(c, launch_plan(c->sd, c->bd, o, pd, static_cast<const PlanRowHdr*>(c->d_plan_hdr), (int)c->plan_rows.size(),
@@ -1656,6 +1650,27 @@ int kad_snapshot_paths(kad_ctx* c, int32_t* out) {
     return KAD_OK;
   });
 }
+
+int kad_route_eval(const int32_t* in, int32_t per_cu, int32_t row_per_cu, int32_t* out) {
+  if (!in || !out) return KAD_EINVAL;
+  RouteIn ri;
+  memcpy(&ri, in, sizeof ri);
+  if (ri.C < 0 || ri.C > 65535 || ri.W < 0 || ri.n_cu < 1) return KAD_EINVAL;
+  Route r = route_schedule(ri);
+  route_grids(ri, r, per_cu, row_per_cu);
+  memcpy(out, &r, sizeof r);
+  return KAD_OK;
+}
+
+int kad_last_route(kad_ctx* c, int32_t* out) {
+  if (!c || !out) return KAD_EINVAL;
+  std::lock_guard<std::mutex> g(c->mu);
+  if (!c->ran) return fail(c, KAD_ESTATE, "nothing ran");
+  memcpy(out, &c->route, sizeof c->route);
+  return KAD_OK;
+}
+
+const char* kad_route_variant_name(int32_t variant) { return variant_name(variant); }
 
 int kad_debug_inject_fault(kad_ctx* c, int where) {
   if (!c || where < 0 || where > 1) return KAD_EINVAL;

@@ -6,6 +6,7 @@
 #include <stdlib.h>
 
 #include "../../include/kad_sched.h"
+#include "kad_route.h"
 
 namespace kad {
 
@@ -159,8 +160,6 @@ constexpr uint32_t REC_DESIRED_POS = 1u << 31;  // DesiredReplicas != nil && *De
 constexpr uint32_t REC_FULL = 1u << 30;         // scheduled by schedule_kernel (features the lean kernel omits)
 constexpr uint32_t REC_ROW = 1u << 29;          // routed to schedule_row_kernel by prep_kernel (BatchDev::early_rows)
 constexpr int ROW_MAX_TERMS = 8;                // schedule_row_kernel: preferred terms held as per-chunk words
-constexpr int WIDE_Q = 8;                       // schedule_wide_kernel: positions per lane
-constexpr int WIDE_P = WIDE_Q * 64;             //   and per wave (longer feasible lists: schedule_row_kernel)
 
 struct OutDev {
   int32_t* status;
@@ -208,9 +207,6 @@ hipError_t launch_trigger_objects(const TriggerDev& t, hipStream_t st);
 
 // bytes of per-wave scratch for the filter/score/select kernel at C clusters
 size_t select_wave_bytes(int C);
-// true if schedule_row_kernel can take the long feasible lists of this snapshot (C <= ROW_MAX_C)
-bool row_kernel_fits(int C);
-constexpr int ROW_MAX_BLOCKS = 1024;  // schedule_row_kernel grid cap (its global slabs are sized for it)
 __host__ __device__ size_t row_slab_bytes(int C);
 size_t plan_wave_bytes(int K);
 
@@ -242,20 +238,29 @@ hipError_t launch_value_rows(const SnapDev& s, uint64_t* vrows, hipStream_t st);
 hipError_t launch_res_cols(const SnapDev& s, void* buf, hipStream_t st);
 inline size_t res_cols_pns4_offset(int C) { return ((size_t)40 * C + 255) & ~(size_t)255; }
 inline size_t res_cols_bytes(int C) { return res_cols_pns4_offset(C) + (size_t)32 * C; }
-// true if the batch runs on schedule_lean_kernel (+ schedule_kernel over its
-// defer list); then launch_prep must run between launch_req_masks and launch_schedule.
-bool fast_path(int C);
-// true if launch_schedule runs schedule_wide_kernel for this snapshot (clean, 5..16 chunks)
-bool wide_path(const SnapDev& s);
-// prep_kernel lanes per unit (a power of two <= 64 lets it count a unit's feasible clusters in one wave)
-int prep_lanes_per_unit(int C);
-hipError_t launch_prep(const SnapDev& s, const BatchDev& b, const ProfDev& p, bool force_full, hipStream_t st);
+// Which kernels a schedule runs is decided by route_schedule (kad_route.h); launch_prep and launch_schedule
+// execute its Route. launch_prep runs between launch_req_masks and launch_schedule, every time.
+// The tuning fields of a RouteIn (measurement builds: from the environment, read per launch)
+inline void route_tuning(RouteIn& in) {
+  in.no_rows = tuning_env("KAD_NO_ROWS", in.no_rows) != 0;
+  in.rows_after = tuning_env("KAD_ROWS_AFTER", in.rows_after) != 0;
+  in.rows_no_inline = tuning_env("KAD_ROWS_NO_INLINE", in.rows_no_inline) != 0;
+  in.prep_wave = tuning_env("KAD_PREP_WAVE", in.prep_wave) != 0;
+  in.wide_min_nch = tuning_env("KAD_WIDE_MIN_NCH", in.wide_min_nch);
+  in.lean_blocks_per_cu = tuning_env("KAD_LEAN_BLOCKS_PER_CU", in.lean_blocks_per_cu);
+}
+// true if route_schedule picks schedule_wide_kernel for this snapshot (clean, 5..16 chunks)
+inline bool wide_path(const SnapDev& s) { return route_wide(s.C, s.clean, tuning_env("KAD_WIDE_MIN_NCH", RouteIn{}.wide_min_nch)); }
+int n_cus();  // of the current device
+hipError_t launch_prep(const SnapDev& s, const BatchDev& b, const ProfDev& p, bool force_full, const Route& r,
+                       hipStream_t st);
+// r: route_schedule's; its grids are filled in here (route_grids, after the occupancy queries).
 // after_main / after_rows (optional): recorded after the main schedule kernel and after the long-row
-// kernel, before the defer pass (stage timing)
-hipError_t launch_schedule(const SnapDev& s, const BatchDev& b, const OutDev& o, const ProfDev& p,
-                           void* global_scratch, size_t scratch_bytes, hipStream_t st, hipEvent_t after_main = nullptr,
-                           hipEvent_t after_rows = nullptr, hipStream_t side = nullptr, hipEvent_t fork = nullptr,
-                           hipEvent_t join = nullptr);
+// kernel, before the defer pass (stage timing); side, fork, join: the row kernel's stream (ROWS_BESIDE)
+hipError_t launch_schedule(const SnapDev& s, const BatchDev& b, const OutDev& o, const ProfDev& p, const RouteIn& in,
+                           Route& r, void* global_scratch, size_t scratch_bytes, hipStream_t st,
+                           hipEvent_t after_main = nullptr, hipEvent_t after_rows = nullptr, hipStream_t side = nullptr,
+                           hipEvent_t fork = nullptr, hipEvent_t join = nullptr);
 // One planner row's unit-level operands, gathered once per batch upload (plan_hdr_kernel) from the batch's
 // per-unit arrays so that plan_kernel reads one 64-B line per row (its lanes 0..15 hold the dwords) instead
 // of ten scattered per-unit loads one dependent step before everything else.

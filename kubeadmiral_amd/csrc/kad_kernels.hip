@@ -76,44 +76,7 @@ __device__ unsigned long long g_uinfo[KAD_UTRACE_MAX];
 #define KAD_PFLUSH
 #endif
 
-// ----------------------------------------------------------- per-wave layout
-struct RowLayout {
-  size_t tot, fx, idx, perm, posl, posr, feas, sel, place, cur, hist, bytes;
-};
-__host__ __device__ inline RowLayout row_layout(int C) {
-  const size_t Cp = (size_t)((C + 63) & ~63);
-  const size_t nw = Cp / 64;
-  RowLayout L;
-  L.tot = 0;                                     // i64[Cp] total per feasible position
-  L.fx = L.tot + 8 * Cp;                         // u32[Cp] fixed scores | TT raw << 16
-  L.idx = L.fx + 4 * Cp;                         // u16[Cp] feasible position → cluster id
-  L.perm = L.idx + 2 * Cp;                       // u16[Cp] pdqsort replay permutation
-  L.posl = L.perm + 2 * Cp;                      // u16[Cp] replay scratch (partition stoppers)
-  L.posr = L.posl + 2 * Cp + 128;                // u16[Cp] (posl: Cp + 64 entries, PdqWave)
-  L.feas = (L.posr + 2 * Cp + 15) & ~(size_t)15;  // u64[nw] feasibility by cluster
-  L.sel = L.feas + 8 * nw;                       // u64[nw] selection by position
-  L.place = L.sel + 8 * nw;
-  L.cur = L.place + 8 * nw;
-  L.hist = L.cur + 8 * nw;
-  L.bytes = (L.hist + 4 * 256 + 15) & ~(size_t)15;
-  return L;
-}
 size_t select_wave_bytes(int C) { return row_layout(C).bytes; }
-// GSCR rows (state in a global slab): the small per-wave arrays that take atomics — selection, placement
-// and current-cluster bitmaps, the radix histogram — stay in LDS (dynamic LDS of the 1-wave blocks)
-struct SmallLayout {
-  size_t sel, place, cur, hist, bytes;
-};
-__host__ __device__ inline SmallLayout small_layout(int C) {
-  const size_t nw = (size_t)((C + 63) / 64);
-  SmallLayout L;
-  L.sel = 0;
-  L.place = 8 * nw;
-  L.cur = 16 * nw;
-  L.hist = 24 * nw;
-  L.bytes = L.hist + 4 * 256;
-  return L;
-}
 
 // ---------------------------------------------------------- predicate programs
 // labels.Requirement.Matches / fields one-term selectors (apimachinery v0.26.6) per interned
@@ -463,7 +426,7 @@ __global__ __launch_bounds__(256) void schedule_kernel(SchedArgs args) {
     region = GSCR ? a->gscratch + (size_t)gw * wbytes : smem + (size_t)wv * wbytes;
     C = a->s.C;
     TW = a->s.TW;
-    W = a->list ? *a->list_n : a->b.W;
+    W = a->list ? *a->list_n : a->b.W;  // (no host launch leaves the list out any more: launch_defer_pass alone)
     fm = a->p.filter_mask;
     sm = a->p.score_mask;
     xs_b = (a->p.flags & KAD_PROFILE_XORSHIFT_GO121) ? 7 : 17;
@@ -973,10 +936,6 @@ __device__ __forceinline__ int2 fit_ranks(const SnapDev& s, const int64_t (*fenc
   return make_int2(b0, b1);
 }
 
-#ifndef KAD_PREP_CPL
-#define KAD_PREP_CPL 4
-#endif
-constexpr int PREP_CPL = KAD_PREP_CPL;                 // chunks per lane
 #ifndef KAD_PREP_MINW
 #define KAD_PREP_MINW 1
 #endif
@@ -1243,13 +1202,7 @@ __global__ __launch_bounds__(256) void prep_wave_kernel(SnapDev s, BatchDev b, P
   }
 }
 
-int prep_lanes_per_unit(int C) {
-  const int nch = (C + 63) >> 6;
-  return nch > 0 ? (nch + PREP_CPL - 1) / PREP_CPL : 1;
-}
-
 // ====================================================== unit work queue
-constexpr int WQ_BATCH = 4;  // units per dequeue
 static_assert(WQ_HEADS == 64, "drained-head set is one u64; heads map to XCDs by h & 7");
 // Work queue: WQ_HEADS = 64 heads; head h hands out the batches of the h-th contiguous 64th of the
 // units. 64 counters (not 8) spread the returning atomics over as many lines: the device-scope
@@ -1313,8 +1266,8 @@ __device__ __forceinline__ int2 wq_resolve(uint32_t* heads, int W, WorkTicket& t
 }
 
 // ================================================= lean schedule kernel
-// schedule_lean_kernel<NCH, CL> — the common case, used whenever C fits the
-// per-wave LDS budget (fast_path). Each wave owns a run of consecutive units.
+// schedule_lean_kernel<NCH, CL> — the common case: every snapshot the wide kernel
+// does not take (kad_route.h route_schedule). Each wave owns a run of consecutive units.
 // For NCH > 0 (C <= 64*NCH) the block first copies the cluster attributes the
 // path reads (fit resources, taint words, GVK word) into an LDS cache shared
 // by its waves; a unit's record and static filter words arrive in VGPRs with
@@ -1335,33 +1288,6 @@ __device__ __forceinline__ int2 wq_resolve(uint32_t* heads, int W, WorkTicket& t
 //     keys (total - row minimum) in the wave's LDS region.
 // Units routed REC_FULL by prep, or (NCH == 0) with more than 64*QMAX
 // feasible clusters, go to the defer list and schedule_kernel afterwards.
-constexpr int LEAN_QMAX_DYN = 4;
-constexpr int LEAN_BATCH = 4;  // units per work-queue batch (one VGPR of UnitRecs)
-static_assert(LEAN_BATCH == WQ_BATCH, "the lean kernel dequeues WQ_BATCH units per ticket");
-__host__ __device__ constexpr int lean_qmax(int nch_t) { return nch_t > 0 ? nch_t : LEAN_QMAX_DYN; }
-// cached attributes: alloc/used cpu & mem, NS|NE taints, GVK word 0 (always),
-// NE taints (taint filter and some unit has CurrentClusters), PNS taints (TaintToleration score)
-struct LeanLayout {
-  size_t key, idx, pid, posl, posr, bytes;
-};
-// per-wave region
-__host__ __device__ inline LeanLayout lean_layout(int C, int qmax) {
- (void)C;
-  const size_t P = (size_t)qmax * 64;  // positions held in registers
-  LeanLayout L;
-  L.key = 0;                     // u32[P] replay keys (total - row minimum)
-  L.idx = L.key + 4 * P;         // u16[P] feasible position → cluster id (NCH > 0: P = Cp)
-  L.posl = L.idx;                // u16[P + 64] replay scratch (partition stoppers; then ranks): idx is
-                                 // dead once the scores have read the cluster ids into registers
-  L.pid = L.idx + 2 * P + 128;   // u16[P] replay: original position at each position
-  L.posr = L.pid + 2 * P;        // u16[P]
-  L.bytes = (L.posr + 2 * P + 15) & ~(size_t)15;
-  return L;
-}
-// block-shared cluster cache (NCH > 0): n_attrs arrays of Cp i64
-__host__ __device__ inline size_t lean_cache_bytes(int C, int n_attrs) { return (size_t)n_attrs * 8 * ((C + 63) & ~63); }
-static constexpr int LDS_BUDGET = 64 * 1024;  // per block
-bool fast_path(int C) { return C >= 0; }  // the lean kernel runs for every C; the full kernel takes its defer list
 
 struct LeanArgs {
   SnapDev s;
@@ -2122,13 +2048,8 @@ __global__ __launch_bounds__(256, 6) void schedule_lean_kernel(LeanArgs args) {
 //     lean kernel (all ties / n <= 12 insertionSort / PdqWave replay).
 // Units with more than WIDE_P feasible clusters, REC_FULL units and requests
 // outside the exact-f64 range go to the defer list (schedule_kernel).
-constexpr int WIDE_MAX_NCH = 16;
-constexpr int WIDE_THREADS = 1024;
 #ifndef KAD_DUMMY_STRIDE
 #define KAD_DUMMY_STRIDE 1  // u16 dummy slots of the wide kernel's compaction: P + stride * lane (<= 2: inside idx / pid)
-#endif
-#ifndef KAD_WIDE_ZS
-#define KAD_WIDE_ZS 1  // the wide kernel's per-cluster zero-request resource scores (c_zs)
 #endif
 #ifndef KAD_WIDE_C8
 #define KAD_WIDE_C8 0  // compaction at exactly 8 chunks: 0 chunk loop, 1 8-cluster lane pieces, 2 16-cluster pieces
@@ -2141,29 +2062,6 @@ __device__ __forceinline__ void row_units(ArgsOf args, char* smem, int rexp);
 template <int SM>
 __device__ __attribute__((noinline)) void wide_rows(char* smem, const __attribute__((address_space(4))) struct WideArgs* a);
 
-struct WideLayout {
-  size_t key, idx, pid, posl, posr, bytes;
-};
-__host__ __device__ inline WideLayout wide_layout() {
-  WideLayout L;
-  L.key = 0;                      // u32[P] replay keys / histogram
-  L.idx = L.key + 4 * WIDE_P;     // u16[P] position -> cluster id
-  L.posl = L.idx;                 // u16[P + 64] replay scratch, then ranks (idx is dead by then: the
-                                  // cluster ids are in registers)
-  L.pid = L.idx + 2 * WIDE_P + 128;  // u16[P] replay: original position
-  L.posr = L.pid + 2 * WIDE_P;    // u16[P]
-  L.bytes = L.posr + 2 * WIDE_P;
-  return L;
-}
-// the compaction stores every feasible cluster's id at its position, even past P (up to 64*nch):
-// those land in pid / posr of the same wave's region and the unit is deferred
-static_assert(2 * 64 * WIDE_MAX_NCH <= 6 * WIDE_P, "idx overflow past P must stay in the wave's region");
-// block-shared cluster cache: av (f64 x2), tg (u64 x2: NS|NE taints, GVK word),
-// cap (f64 x2), iv (f32 x2), [ne u64], [pn u64]
-__host__ __device__ inline size_t wide_cache_bytes(int C, int cache_ne, int cache_pn, int cache_zs = 0) {
-  const size_t Cp = (size_t)((C + 63) & ~63);
-  return Cp * (16 + 16 + 16 + 8 + 8 * cache_ne + 8 * cache_pn + 4 * cache_zs);
-}
 
 struct WideArgs {
   SnapDev s;
@@ -2872,12 +2770,6 @@ __global__ __launch_bounds__(WIDE_THREADS, 4) void schedule_wide_kernel(WideArgs
 //   * output in ascending cluster id by per-chunk ballots and a block prefix.
 // Units outside the clean-f64 range (requests >= 2^46, wide affinity weights) or with more than
 // ROW_MAX_TERMS preferred terms go on to the defer list.
-constexpr int ROW_THREADS = 512;
-constexpr int ROW_WAVES = ROW_THREADS / 64;
-constexpr int ROW_MAX_WAVES = 16;  // the row body also runs on schedule_wide_kernel's 1024-thread blocks
-constexpr int ROW_MAX_C = 12288;
-constexpr int ROW_NREP = 2048;    // replays of up to this many positions keep their scratch in LDS
-constexpr int ROW_BLOCK_PART = 256;  // replay partitions of longer ranges run on every wave of the block
 #ifndef KAD_ROW_RU
 #define KAD_ROW_RU 2
 #endif
@@ -2889,33 +2781,6 @@ constexpr int ROW_BLOCK_PART = 256;  // replay partitions of longer ranges run o
 // rows 1.28 -> 1.30 ms, two product builds on one box); 4 spills and drops to one block per CU
 constexpr int ROW_RU = KAD_ROW_RU;
 static_assert(ROW_MAX_BLOCKS >= 1, "row kernel slabs");
-struct RowKLayout {
-  size_t key, idx, x, pid, posl, posr, sw, cnt, hist, red, pre, bytes;
-};
-// a unit's staged record and score program (u32[2][ROW_PRE_DW], the next unit's prefetched into the other
-// buffer): its UnitRec dwords, the program length, then its first ROW_PRE_PROG program words
-constexpr int ROW_PRE_PROG = 64, ROW_PRE_DW = 16 + 1 + ROW_PRE_PROG + 15;
-__host__ __device__ inline RowKLayout rowk_layout(int C) {
-  const size_t Cp = (size_t)((C + 63) & ~63), nch = Cp / 64;
-  RowKLayout L;
-  L.key = 0;                              // u32[Cp]: fixed | TT raw << 16, then totals (sign-flipped), replay keys
-  L.idx = L.key + 4 * Cp;                 // u16[Cp]: position → cluster id
-  L.x = L.idx + 2 * Cp;                   // preferred-term words u64[8][nch] while scoring, then the replay
-  L.pid = L.x;                            //   scratch: pid u16[NREP], posl u16[NREP + 64], posr u16[NREP]
-  L.posl = L.pid + 2 * ROW_NREP;
-  L.posr = L.posl + 2 * ROW_NREP + 128;
-  const size_t xb = Cp > 6 * (size_t)ROW_NREP + 128 ? Cp : 6 * (size_t)ROW_NREP + 128;
-  L.sw = (L.x + xb + 15) & ~(size_t)15;   // u64[2][nch]: the unit's static words (two buffers: the next
-  L.cnt = L.sw + 16 * nch;                //   unit's are prefetched); i32[2][nch + 1]: chunk counts →
-                                          //   exclusive prefix (+ total)
-  L.hist = (L.cnt + 8 * (nch + 1) + 15) & ~(size_t)15;  // u32[256]
-  L.red = L.hist + 4 * 256;               // i32[4][ROW_MAX_WAVES] per-wave partials, i32[24] broadcasts
-  L.pre = L.red + 4 * (4 * ROW_MAX_WAVES + 24);  // u32[2][ROW_PRE_DW]: staged records + score programs
-  L.bytes = L.pre + 4 * 2 * ROW_PRE_DW;
-  return L;
-}
-size_t row_kernel_lds(int C) { return rowk_layout(C).bytes; }
-bool row_kernel_fits(int C) { return C > 0 && C <= ROW_MAX_C; }
 // per-block global slab for replays longer than ROW_NREP: pid u16[Cp], posl u16[Cp + 64], posr u16[Cp]
 __host__ __device__ size_t row_slab_bytes(int C) { return ((size_t)6 * ((C + 63) & ~63) + 128 + 255) & ~(size_t)255; }
 
@@ -4424,282 +4289,124 @@ hipError_t launch_slices(const SnapDev& s, uint64_t* slices, hipStream_t st) {
   return hipGetLastError();
 }
 
-hipError_t launch_prep(const SnapDev& s, const BatchDev& b, const ProfDev& p, bool force_full, hipStream_t st) {
+// The prep and schedule kernels by route id (kad_route.h: PREP*, KAD_VARIANTS): the one list of their
+// instantiations, for the LDS attribute, the occupancy queries and the launches.
+static void (*const PREP_FN[4])(SnapDev, BatchDev, ProfDev, int) = {prep_kernel, prep_wave_kernel<2>, prep_wave_kernel<3>,
+                                                                    prep_wave_kernel<4>};
+#define X(n, ...) (const void*)__VA_ARGS__,
+static const void* const VARIANT_FN[KV_COUNT] = {KAD_VARIANTS(X)};
+#undef X
+// the argument struct the launchers cast each family's entries back to
+template <int V>
+using VariantArgs = std::conditional_t<V <= KV_FULL_GSCR, SchedArgs, std::conditional_t<V <= KV_ROW, RowArgs,
+                    std::conditional_t<V <= KV_WIDE8_DEFAULT, WideArgs, LeanArgs>>>;
+#define X(n, ...) static_assert(std::is_same<decltype(&__VA_ARGS__), void (*)(VariantArgs<KV_##n>)>::value, #n);
+KAD_VARIANTS(X)
+#undef X
+
+hipError_t launch_prep(const SnapDev& s, const BatchDev& b, const ProfDev& p, bool force_full, const Route& r,
+                       hipStream_t st) {
   (void)hipGetLastError();
-  const int nch = (s.C + 63) >> 6;
-  const long lanes = (long)b.W * (nch > 0 ? (nch + PREP_CPL - 1) / PREP_CPL : 1);
-  const long grid = lanes > 0 ? (lanes + 255) / 256 : 1;  // one block at W = 0 still resets defer_n
-  // wide snapshots (more than 64 chunks, up to 256): one unit per wave
-  const int cw = (nch + 63) / 64;
-  if (nch > 64 && cw <= 4 && tuning_env("KAD_PREP_WAVE", 1)) {
-    // (not persistent: C5's one-unit-per-wave prep is L2-miss bound and took 587 -> 729 us with the resident
-    // grid, profiles/r06/ab_c5_prep_persistent.txt)
-    const long wgrid = b.W > 0 ? ((long)b.W + 3) / 4 : 1;
-    const int ff = force_full ? 1 : 0;
-    if (cw == 2) hipLaunchKernelGGL(prep_wave_kernel<2>, dim3((unsigned)wgrid), dim3(256), 0, st, s, b, p, ff);
-    else if (cw == 3) hipLaunchKernelGGL(prep_wave_kernel<3>, dim3((unsigned)wgrid), dim3(256), 0, st, s, b, p, ff);
-    else hipLaunchKernelGGL(prep_wave_kernel<4>, dim3((unsigned)wgrid), dim3(256), 0, st, s, b, p, ff);
-    return hipGetLastError();
-  }
-  hipLaunchKernelGGL(prep_kernel, dim3((unsigned)grid), dim3(256), 0, st, s, b, p, force_full ? 1 : 0);
+  // prep_kernel: prep_lanes lanes per unit; prep_wave_kernel: one unit per wave (not persistent: C5's prep is
+  // L2-miss bound and took 587 -> 729 us with the resident grid, profiles/r06/ab_c5_prep_persistent.txt)
+  const long grid = r.prep == PREP ? ((long)b.W * r.prep_lanes + 255) / 256 : ((long)b.W + 3) / 4;
+  // (one block at W = 0 still resets defer_n)
+  hipLaunchKernelGGL(PREP_FN[r.prep], dim3((unsigned)(grid > 0 ? grid : 1)), dim3(256), 0, st, s, b, p, force_full ? 1 : 0);
   return hipGetLastError();
 }
 
-template <int NCH, bool CL, int SM = -1>
-static void launch_lean(const LeanArgs& A, int grid, size_t lds, hipStream_t st) {
-  hipLaunchKernelGGL((schedule_lean_kernel<NCH, CL, SM>), dim3(grid), dim3(64 * A.waves_per_block), lds, st, A);
-}
-
-static int n_cus() {
+int n_cus() {
   static int n_cu = 0;
-  if (n_cu == 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0) n_cu = 256;
-  }
+  int dev = 0;
+  if (n_cu == 0 && (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0)) n_cu = 256;
   return n_cu;
 }
 
-// the wide kernel takes clean snapshots with WIDE_MIN_NCH <= nch <= WIDE_MAX_NCH
-// (KAD_WIDE_MIN_NCH overrides the lower bound, for A/B runs of C <= 256)
-static bool use_wide(const SnapDev& s) {
-  static int min_nch = -1;
-  if (min_nch < 0) min_nch = tuning_env("KAD_WIDE_MIN_NCH", 5);
-  const int nch = (s.C + 63) >> 6;
-  return s.clean && nch >= min_nch && nch >= 1 && nch <= WIDE_MAX_NCH;
-}
-bool wide_path(const SnapDev& s) { return use_wide(s); }
-
-static hipError_t launch_defer_pass(const SnapDev& s, const BatchDev& b, const OutDev& o, const ProfDev& p, void* gscr,
-                                    size_t scr_bytes, hipStream_t st) {
+// schedule_kernel over the defer list: its length is only known on the device, so the grid strides over it
+// (waves past its end exit at once)
+static hipError_t launch_defer_pass(const SnapDev& s, const BatchDev& b, const OutDev& o, const ProfDev& p, const Route& r,
+                                    void* gscr, size_t scr_bytes, hipStream_t st) {
   const size_t wb = row_layout(s.C).bytes;
-  if (wb <= (size_t)LDS_BUDGET) {
+  const auto fn = (void (*)(SchedArgs))VARIANT_FN[r.full_variant];
+  if (r.full_variant == KV_FULL_LDS) {
     int wpb2 = (int)(LDS_BUDGET / wb);
     wpb2 = wpb2 > 4 ? 4 : (wpb2 < 1 ? 1 : wpb2);
     long waves2 = b.W < 256 * 16 ? b.W : 256 * 16;
     const int grid2 = (int)((waves2 + wpb2 - 1) / wpb2);
     const SchedArgs A2{s, b, o, p, nullptr, (int)wb, wpb2, grid2 * wpb2, b.defer, b.defer_n};
-    hipLaunchKernelGGL(schedule_kernel<false>, dim3(grid2), dim3(64 * wpb2), wb * wpb2, st, A2);
+    hipLaunchKernelGGL(fn, dim3(grid2), dim3(64 * wpb2), wb * wpb2, st, A2);
   } else {  // rows too large for LDS: per-wave global scratch slabs
     size_t slots = scr_bytes / wb;
     if (slots < 1) return hipErrorInvalidValue;
     if (slots > (size_t)MAX_RESIDENT_WAVES) slots = MAX_RESIDENT_WAVES;
     if (slots > (size_t)b.W) slots = b.W;
     const SchedArgs A2{s, b, o, p, (char*)gscr, (int)wb, 1, (int)slots, b.defer, b.defer_n};
-    hipLaunchKernelGGL(schedule_kernel<true>, dim3((int)slots), dim3(64), small_layout(s.C).bytes, st, A2);
+    hipLaunchKernelGGL(fn, dim3((int)slots), dim3(64), small_layout(s.C).bytes, st, A2);
   }
   return hipGetLastError();
 }
 
 // schedule_row_kernel over BatchDev::rows (its length is only known on the device: the persistent
 // workgroups dequeue until the list is drained)
-static hipError_t launch_rows(const SnapDev& s, const BatchDev& b, const OutDev& o, const ProfDev& p, hipStream_t st) {
-  if (!b.use_rows) return hipSuccess;
-  const size_t lds = row_kernel_lds(s.C);
-  constexpr int SM_DEFAULT = (1 << KAD_PL_TAINT_TOLERATION) | (1 << KAD_PL_BALANCED_ALLOCATION) |
-                             (1 << KAD_PL_LEAST_ALLOCATED) | (1 << KAD_PL_CLUSTER_AFFINITY);
-  // the default plugin set's scores as constants (C5), else the generic kernel
-  void (*fn)(RowArgs) = p.score_mask == (uint32_t)SM_DEFAULT ? schedule_row_kernel<SM_DEFAULT> : schedule_row_kernel<-1>;
-  static bool attr = false;
-  if (!attr) {
-    for (const void* f : {(const void*)schedule_row_kernel<SM_DEFAULT>, (const void*)schedule_row_kernel<-1>})
-      if (hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) return e;
-    attr = true;
-  }
-  int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, ROW_THREADS, lds) != hipSuccess || per_cu < 1)
-    per_cu = 1;
-  long grid = (long)n_cus() * per_cu;
-  if (grid > ROW_MAX_BLOCKS) grid = ROW_MAX_BLOCKS;
-  if (grid > b.W) grid = b.W;
-  if (!b.row_slabs) return hipErrorInvalidValue;
+static hipError_t launch_rows(const SnapDev& s, const BatchDev& b, const OutDev& o, const ProfDev& p, const Route& r,
+                              hipStream_t st) {
   static const int exp = tuning_env("KAD_ROW_EXPERIMENT", 0);
   const RowArgs A{s, b, o, p, b.row_slabs, exp};
-  hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(ROW_THREADS), lds, st, A);
+  hipLaunchKernelGGL((void (*)(RowArgs))VARIANT_FN[r.row_variant], dim3((unsigned)r.row_grid), dim3(ROW_THREADS),
+                     row_kernel_lds(s.C), st, A);
   return hipGetLastError();
 }
 
-hipError_t launch_schedule(const SnapDev& s, const BatchDev& b, const OutDev& o, const ProfDev& p, void* gscr,
-                           size_t scr_bytes, hipStream_t st, hipEvent_t after_main, hipEvent_t after_rows,
-                           hipStream_t side, hipEvent_t fork, hipEvent_t join) {
+hipError_t launch_schedule(const SnapDev& s, const BatchDev& b, const OutDev& o, const ProfDev& p, const RouteIn& in,
+                           Route& r, void* gscr, size_t scr_bytes, hipStream_t st, hipEvent_t after_main,
+                           hipEvent_t after_rows, hipStream_t side, hipEvent_t fork, hipEvent_t join) {
   auto rec = [&](hipEvent_t ev) { return ev ? hipEventRecord(ev, st) : hipSuccess; };
   (void)hipGetLastError();  // clear any stale error so the check below is this launch's
   if (b.W == 0) return hipSuccess;
-  const size_t wb = row_layout(s.C).bytes;
-  if (use_wide(s)) {
-    const int cache_ne = (p.filter_mask & (1u << KAD_PL_TAINT_TOLERATION)) && (b.flags_or & KAD_W_HAS_CURRENT);
-    const int cache_pn = (p.score_mask >> KAD_PL_TAINT_TOLERATION) & 1;
-    const size_t per_wave = wide_layout().bytes;
-    const size_t lds_max = 160 * 1024;
-    const bool s_res = p.score_mask & ((1u << KAD_PL_LEAST_ALLOCATED) | (1u << KAD_PL_MOST_ALLOCATED) |
-                                       (1u << KAD_PL_BALANCED_ALLOCATION));
-    // zero-request batches: the resource-score column, when it costs no wave (LDS beside the 16 wave regions)
-    const int cache_zs = (KAD_WIDE_ZS && s_res && b.zero_req &&
-                          wide_cache_bytes(s.C, cache_ne, cache_pn, 1) + (size_t)(WIDE_THREADS / 64) * per_wave <= lds_max)
-                             ? 1
-                             : 0;
-    const size_t cache = wide_cache_bytes(s.C, cache_ne, cache_pn, cache_zs);
-    int wpb = (int)((lds_max - cache) / per_wave);
-    wpb = wpb > WIDE_THREADS / 64 ? WIDE_THREADS / 64 : wpb;
-    if (wpb < 1) return hipErrorInvalidValue;
-    const size_t lds = cache + (size_t)wpb * per_wave;
-    // the instantiation: the score set of the bench profiles (C2/C3: LeastAllocated alone; C4: the default set,
-    // also at its exact 8 chunks — 16 exact chunks unroll past the 128-VGPR budget and spill), else generic
-    const int nch = (s.C + 63) >> 6;
-    constexpr int SM_LEAST = 1 << KAD_PL_LEAST_ALLOCATED;
-    constexpr int SM_DEFAULT = (1 << KAD_PL_TAINT_TOLERATION) | (1 << KAD_PL_BALANCED_ALLOCATION) |
-                               (1 << KAD_PL_LEAST_ALLOCATED) | (1 << KAD_PL_CLUSTER_AFFINITY);
-    const bool zr = cache_zs != 0;
-    const void* fn = zr ? (const void*)schedule_wide_kernel<WIDE_MAX_NCH, 0, -1, true>
-                        : (const void*)schedule_wide_kernel<WIDE_MAX_NCH, 0, -1>;
-    const bool folded = s.fold && s.fitfold;  // the LeastAllocated specialisation compiles the folded filter only
-    if (folded && nch == 16 && p.score_mask == (uint32_t)SM_LEAST)
-      fn = zr ? (const void*)schedule_wide_kernel<WIDE_MAX_NCH, 0, SM_LEAST, true>
-              : (const void*)schedule_wide_kernel<WIDE_MAX_NCH, 0, SM_LEAST>;
-    else if (nch == 8 && p.score_mask == (uint32_t)SM_DEFAULT)
-      fn = zr ? (const void*)schedule_wide_kernel<8, 8, SM_DEFAULT, true> : (const void*)schedule_wide_kernel<8, 8, SM_DEFAULT>;
-    static bool attr = false;
-    if (!attr) {
-      for (const void* f : {(const void*)schedule_wide_kernel<WIDE_MAX_NCH, 0, -1>,
-                            (const void*)schedule_wide_kernel<WIDE_MAX_NCH, 0, SM_LEAST>,
-                            (const void*)schedule_wide_kernel<8, 8, SM_DEFAULT>,
-                            (const void*)schedule_wide_kernel<WIDE_MAX_NCH, 0, -1, true>,
-                            (const void*)schedule_wide_kernel<WIDE_MAX_NCH, 0, SM_LEAST, true>,
-                            (const void*)schedule_wide_kernel<8, 8, SM_DEFAULT, true>})
-        if (hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max)) return e;
-      attr = true;
-    }
-    long grid = n_cus();
-    const long need = ((long)b.W + wpb - 1) / wpb;
-    if (grid > need) grid = need;
+  if (r.wpb < 1) return hipErrorInvalidValue;
+  const bool beside = r.rows == ROWS_BESIDE, row_launch = beside || r.rows == ROWS_AFTER;
+  // Up front, where the parent did them beside each launch: the row and wide kernels' LDS limit (all eight at the
+  // first launch that runs one), the slab check and both occupancy queries — before any kernel is launched.
+  static bool attr = false;
+  if (!attr && (row_launch || r.family == FAMILY_WIDE)) {
+    for (int v = KV_ROW_DEFAULT; v <= KV_WIDE8_DEFAULT; ++v)
+      if (hipError_t e = hipFuncSetAttribute(VARIANT_FN[v], hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX)) return e;
+    attr = true;
+  }
+  if (row_launch && !b.row_slabs) return hipErrorInvalidValue;
+  auto per_cu = [](const void* fn, int threads, size_t lds) {  // (a failed query: 0, which route_grids takes as 1)
+    int n = 0;
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, threads, lds) == hipSuccess ? n : 0;
+  };
+  route_grids(in, r, r.family == FAMILY_LEAN ? per_cu(VARIANT_FN[r.variant], r.threads, r.lds) : 0,
+              row_launch ? per_cu(VARIANT_FN[r.row_variant], ROW_THREADS, row_kernel_lds(s.C)) : 0);
+  if (beside) {  // the row kernel on the side stream, from the end of prep_kernel, beside the wide kernel
+    if (hipError_t e = hipEventRecord(fork, st)) return e;
+    if (hipError_t e = hipStreamWaitEvent(side, fork, 0)) return e;
+    if (hipError_t e = launch_rows(s, b, o, p, r, side)) return e;
+    if (hipError_t e = hipEventRecord(join, side)) return e;
+  }
+  if (r.family == FAMILY_WIDE) {
     static const int exp = tuning_env("KAD_WIDE_EXPERIMENT", 0);
-    // the routed long units inside the wide kernel (its opening phase) when the row body's LDS fits below
-    // the cluster cache; else the row kernel beside it on a second stream
-    const int no_inline = tuning_env("KAD_ROWS_NO_INLINE", 0);  // (read per launch: tuning builds only)
-    // (the row body needs >= 2 waves: wave 1 dequeues and prefetches while wave 0 replays)
-    const bool inline_rows = b.early_rows && b.use_rows && !no_inline && wpb >= 2 &&
-                             row_kernel_lds(s.C) <= (size_t)wpb * per_wave;
-    // work-queue batch: 4 units, 3 when the waves take fewer than 64 units each (a 125k-unit shard: the last
-    // batches are the tail; at 1M units 3-unit batches cost more in dequeue atomics than they save:
-    // profiles/r05/ab_wide_batch_c3.txt)
-    const long upw = ((long)b.W + grid * wpb - 1) / (grid * wpb);
-    const int wbatch = upw < 64 ? 3 : WQ_BATCH;
-    const WideArgs A{s, b, o, p, wpb, cache_ne, cache_pn, cache_zs, inline_rows ? 1 : 0, wbatch, exp};
-    const bool beside = !inline_rows && b.early_rows && b.use_rows && side && fork && join;
-    if (beside) {  // the row kernel on the side stream, from the end of prep_kernel, beside the wide kernel
-      if (hipError_t e = hipEventRecord(fork, st)) return e;
-      if (hipError_t e = hipStreamWaitEvent(side, fork, 0)) return e;
-      if (hipError_t e = launch_rows(s, b, o, p, side)) return e;
-      if (hipError_t e = hipEventRecord(join, side)) return e;
-    }
-    hipLaunchKernelGGL((void (*)(WideArgs))fn, dim3((unsigned)grid), dim3(64 * wpb), lds, st, A);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = rec(after_main);
-    if (beside) {
-      // joined even when the wide launch failed: the row kernel on the side stream must finish before
-      // anything later on st (the next batch upload) can overwrite what it reads
-      const hipError_t j = hipStreamWaitEvent(st, join, 0);
-      if (e == hipSuccess) e = j;
-    } else if (e == hipSuccess && !inline_rows) {
-      e = launch_rows(s, b, o, p, st);
-    }
-    if (e != hipSuccess) return e;
-    if (hipError_t e2 = rec(after_rows)) return e2;
-    // the defer pass only when some unit can reach the defer list (BatchDev::may_defer, host-checked:
-    // REC_FULL units, requests or affinity weights outside the exact path, rows with more preferred terms
-    // than ROW_MAX_TERMS, or units past WIDE_P without early routing)
-    if (!b.may_defer) return hipSuccess;
-    return launch_defer_pass(s, b, o, p, gscr, scr_bytes, st);
-  }
-  if (fast_path(s.C)) {
-    const int nch = (s.C + 63) >> 6;
-    const size_t lb = lean_layout(s.C, lean_qmax(nch <= 4 ? nch : 0)).bytes;
-    const int wpb = 4;
-    // runs of consecutive units per wave: long enough to amortise the
-    // register-resident cluster attributes, short enough that the grid is
-    // many times the resident wave count
-    const int cache_ne = (p.filter_mask & (1u << KAD_PL_TAINT_TOLERATION)) && (b.flags_or & KAD_W_HAS_CURRENT);
-    const int cache_pn = (p.score_mask >> KAD_PL_TAINT_TOLERATION) & 1;
-    const size_t lds = lb * wpb + (nch <= 4 ? lean_cache_bytes(s.C, 6 + cache_ne + cache_pn + ((s.clean && nch >= 1 && nch <= 4) ? 1 : 0)) : 0);
-    // one wave per resident slot: contiguous equal shares, no tail of late blocks
-    const int n_cu = n_cus();
-    int per_cu = 0;
-    hipError_t oe;
-    const bool cl = s.clean && nch >= 1 && nch <= 4;
-    // score-set specialisations of the bench profiles: C2 (4 clean chunks, LeastAllocated alone), C5 (long
-    // lists, the default set)
-    constexpr int SM_LEAST = 1 << KAD_PL_LEAST_ALLOCATED;
-    constexpr int SM_DEFAULT = (1 << KAD_PL_TAINT_TOLERATION) | (1 << KAD_PL_BALANCED_ALLOCATION) |
-                               (1 << KAD_PL_LEAST_ALLOCATED) | (1 << KAD_PL_CLUSTER_AFFINITY);
-    const bool least4 = cl && nch == 4 && p.score_mask == (uint32_t)SM_LEAST;
-    const bool def0 = nch > 4 && p.score_mask == (uint32_t)SM_DEFAULT;
-#define KAD_OCC(N, B) hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, schedule_lean_kernel<N, B>, 64 * wpb, lds)
-    switch (nch) {
-      case 1: oe = cl ? KAD_OCC(1, true) : KAD_OCC(1, false); break;
-      case 2: oe = cl ? KAD_OCC(2, true) : KAD_OCC(2, false); break;
-      case 3: oe = cl ? KAD_OCC(3, true) : KAD_OCC(3, false); break;
-      case 4:
-        oe = least4 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, schedule_lean_kernel<4, true, SM_LEAST>,
-                                                                    64 * wpb, lds)
-                    : (cl ? KAD_OCC(4, true) : KAD_OCC(4, false));
-        break;
-      default:
-        oe = def0 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, schedule_lean_kernel<0, false, SM_DEFAULT>,
-                                                                  64 * wpb, lds)
-                  : KAD_OCC(0, false);
-        break;
-    }
-#undef KAD_OCC
-    if (oe != hipSuccess || per_cu < 1) per_cu = 1;
-    per_cu = tuning_env("KAD_LEAN_BLOCKS_PER_CU", per_cu);
-    long grid = (long)n_cu * per_cu;
-    const long need = ((long)b.W + wpb - 1) / wpb;  // at least one unit per wave
-    if (grid > need) grid = need;
-    // units per work-queue batch: at most LEAN_BATCH (one VGPR of UnitRecs), small enough that every wave
-    // takes >= 12 batches, so the waves run out of work together (C2: 16 units per wave → 1-unit batches)
-    const long upw = ((long)b.W + grid * wpb - 1) / (grid * wpb);
-    int bsz = (int)(upw / 6);
-    bsz = bsz < 1 ? 1 : (bsz > LEAN_BATCH ? LEAN_BATCH : bsz);
-    const LeanArgs A{s, b, o, p, (int)lb, wpb, bsz, cache_ne, cache_pn};
-    switch (nch) {
-      case 1: cl ? launch_lean<1, true>(A, (int)grid, lds, st) : launch_lean<1, false>(A, (int)grid, lds, st); break;
-      case 2: cl ? launch_lean<2, true>(A, (int)grid, lds, st) : launch_lean<2, false>(A, (int)grid, lds, st); break;
-      case 3: cl ? launch_lean<3, true>(A, (int)grid, lds, st) : launch_lean<3, false>(A, (int)grid, lds, st); break;
-      case 4:
-        if (least4)
-          launch_lean<4, true, SM_LEAST>(A, (int)grid, lds, st);
-        else
-          cl ? launch_lean<4, true>(A, (int)grid, lds, st) : launch_lean<4, false>(A, (int)grid, lds, st);
-        break;
-      default: def0 ? launch_lean<0, false, SM_DEFAULT>(A, (int)grid, lds, st) : launch_lean<0, false>(A, (int)grid, lds, st); break;
-    }
-    if (hipError_t e = hipGetLastError()) return e;
-    if (hipError_t e = rec(after_main)) return e;
-    // nothing can be deferred (host-checked: every unit and cluster is in the
-    // lean kernel's range and every feasible list fits its registers)
-    if (nch <= 4 && !b.may_defer) return rec(after_rows);
-    if (nch > 4)
-      if (hipError_t e = launch_rows(s, b, o, p, st)) return e;
-    if (hipError_t e = rec(after_rows)) return e;
-    // the defer list: its length is only known on the device, so the grid
-    // strides over it (waves past its end exit at once)
-    return launch_defer_pass(s, b, o, p, gscr, scr_bytes, st);
-  }
-  if (wb <= (size_t)LDS_BUDGET) {
-    int wpb = (int)(LDS_BUDGET / wb);
-    wpb = wpb > 4 ? 4 : (wpb < 1 ? 1 : wpb);
-    const int grid = (b.W + wpb - 1) / wpb;
-    const SchedArgs A{s, b, o, p, nullptr, (int)wb, wpb, grid * wpb, nullptr, nullptr};
-    hipLaunchKernelGGL(schedule_kernel<false>, dim3(grid), dim3(64 * wpb), wb * wpb, st, A);
+    const WideArgs A{s, b, o, p, r.wpb, r.cache_ne, r.cache_pn, r.cache_zs, r.rows == ROWS_INLINE ? 1 : 0, r.batch, exp};
+    hipLaunchKernelGGL((void (*)(WideArgs))VARIANT_FN[r.variant], dim3((unsigned)r.grid), dim3(r.threads), r.lds, st, A);
   } else {
-    size_t slots = scr_bytes / wb;
-    if (slots < 1) return hipErrorInvalidValue;
-    if (slots > (size_t)MAX_RESIDENT_WAVES) slots = MAX_RESIDENT_WAVES;
-    if (slots > (size_t)b.W) slots = b.W;
-    const int grid = (int)slots;
-    const SchedArgs A{s, b, o, p, (char*)gscr, (int)wb, 1, grid, nullptr, nullptr};
-    hipLaunchKernelGGL(schedule_kernel<true>, dim3(grid), dim3(64), small_layout(s.C).bytes, st, A);
+    const LeanArgs A{s, b, o, p, r.wave_bytes, r.wpb, r.batch, r.cache_ne, r.cache_pn};
+    hipLaunchKernelGGL((void (*)(LeanArgs))VARIANT_FN[r.variant], dim3((unsigned)r.grid), dim3(r.threads), r.lds, st, A);
   }
-  return hipGetLastError();
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = rec(after_main);
+  if (beside) {
+    // joined even when the main launch failed: the row kernel on the side stream must finish before
+    // anything later on st (the next batch upload) can overwrite what it reads
+    const hipError_t j = hipStreamWaitEvent(st, join, 0);
+    if (e == hipSuccess) e = j;
+  } else if (e == hipSuccess && row_launch) {
+    e = launch_rows(s, b, o, p, r, st);
+  }
+  if (e != hipSuccess) return e;
+  if (hipError_t e2 = rec(after_rows)) return e2;
+  return r.defer_pass ? launch_defer_pass(s, b, o, p, r, gscr, scr_bytes, st) : hipSuccess;
 }
 
 hipError_t launch_plan_hdr(const BatchDev& b, const int32_t* rows, int n_rows, PlanRowHdr* out, hipStream_t st) {

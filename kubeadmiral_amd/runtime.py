@@ -76,6 +76,41 @@ def declared_functions() -> List[str]:
     return sorted(names)
 
 
+# kad_route_eval's records (include/kad_sched.h): the inputs with the defaults of the tuning fields, the outputs
+ROUTE_IN = dict(C=0, clean=0, fold=0, fitfold=0, TW=1, snap_negative=0, W=1, has_current=0, zero_req=0, batch_defer=0,
+                batch_many_terms=0, filter_mask=0, score_mask=0, debug_capture=0, side_stream=1, n_cu=256, no_rows=0,
+                rows_after=0, rows_no_inline=0, prep_wave=1, wide_min_nch=5, lean_blocks_per_cu=0)
+ROUTE_OUT = ("prep", "prep_lanes", "family", "variant", "row_variant", "full_variant", "use_rows", "early_rows",
+             "may_defer", "rows", "defer_pass", "cache_ne", "cache_pn", "cache_zs", "wpb", "threads", "lds", "wave_bytes",
+             "grid", "batch", "row_grid")
+_ROUTE_ENUMS = {"prep": ("PREP", "PREP_WAVE2", "PREP_WAVE3", "PREP_WAVE4"), "family": ("LEAN", "WIDE"),
+                "rows": ("NONE", "INLINE", "BESIDE", "AFTER")}
+
+
+def _route_dict(L, out) -> dict:
+    d = dict(zip(ROUTE_OUT, out))
+    for k in ("variant", "row_variant", "full_variant"):
+        d[k] = L.kad_route_variant_name(d[k]).decode()
+    for k, names in _ROUTE_ENUMS.items():
+        d[k] = names[d[k]]
+    return d
+
+
+def route_eval(per_cu: int = 1, row_per_cu: int = 1, **inputs) -> dict:
+    """kad_route_eval: the library's route decision on the given inputs (ROUTE_IN's fields; needs no GPU), with
+    the kernel variants, the prep kernel, the family and the row placement as their enum names."""
+    L = load_library()
+    bad = set(inputs) - set(ROUTE_IN)
+    if bad:
+        raise TypeError(f"unknown route inputs {sorted(bad)}")
+    rin = (ctypes.c_int32 * len(ROUTE_IN))(*[int(inputs.get(k, v)) for k, v in ROUTE_IN.items()])
+    out = (ctypes.c_int32 * len(ROUTE_OUT))()
+    rc = L.kad_route_eval(rin, per_cu, row_per_cu, out)
+    if rc != 0:
+        raise ValueError(f"kad_route_eval: {rc}")
+    return _route_dict(L, out)
+
+
 def load_library(path: str = LIB_PATH):
     """Load libkad.so (fails loudly: the product path has no CPU fallback)."""
     global _lib
@@ -104,6 +139,11 @@ def load_library(path: str = LIB_PATH):
     L.kad_path_counts.argtypes = [P, P]
     if hasattr(L, "kad_snapshot_paths"):  # (absent from libraries of older revisions: A/B runs)
         L.kad_snapshot_paths.argtypes = [P, P]
+    if hasattr(L, "kad_route_eval"):  # (absent from libraries of older revisions: A/B runs)
+        L.kad_route_eval.argtypes = [P, ctypes.c_int32, ctypes.c_int32, P]
+        L.kad_last_route.argtypes = [P, P]
+        L.kad_route_variant_name.argtypes = [ctypes.c_int32]
+        L.kad_route_variant_name.restype = ctypes.c_char_p
     L.kad_result_diff.argtypes = [P, P, P]
     L.kad_schedule_batch.argtypes = [P, P, P, SZ, P]
     L.kad_select_rows.argtypes = [P, I, P, P, P, U32, P, P, P]
@@ -302,6 +342,12 @@ class Context:
         self._chk(self.L.kad_snapshot_paths(self.h, out))
         return {"resource_class": {2: "strict", 1: "relaxed", 0: "generic"}[out[0]], "exact_f64": bool(out[1]),
                 "wide": bool(out[2]), "fold": bool(out[3]), "fitfold": bool(out[4])}
+
+    def last_route(self) -> dict:
+        """kad_last_route: what the last schedule() launched (route_eval's record, grids included)."""
+        out = (ctypes.c_int32 * len(ROUTE_OUT))()
+        self._chk(self.L.kad_last_route(self.h, out))
+        return _route_dict(self.L, out)
 
     def copy_results_device(self, status_ptr: int, count_ptr: int, flags_ptr: int, cluster_ptr: int,
                             replicas_ptr: int):

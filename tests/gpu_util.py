@@ -25,7 +25,7 @@ def assert_same(got, want, what=""):
 
 
 # ------------------------------------------------------------------ boundary inputs
-# Cluster counts at which a launcher of kad_kernels.hip changes kernels (nch = ceil(C / 64)): exact chunk
+# Cluster counts at which the route (kad_route.h) changes kernels (nch = ceil(C / 64)): exact chunk
 # multiples (no tail chunk) and one past them (one live lane in the last chunk).
 SWEEP_CS = [64, 128, 192, 256, 257, 320, 449, 512, 513, 961, 1024, 1025, 4096, 4097, 8192, 8193, 12288, 16384, 16385]
 SWEEP_W = 64

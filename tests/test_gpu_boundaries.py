@@ -1,8 +1,8 @@
 """HIP path == the C oracle at every cluster count C where a launcher changes kernels, bit for bit.
 
-nch = ceil(C / 64) decides the route (kad_kernels.hip launch_prep / launch_schedule / launch_rows /
-launch_defer_pass, kad_explain.hip launch_explain); each boundary below is run on both of its sides, and the
-route is asserted from the library's own reporting (snapshot_paths, path_counts):
+nch = ceil(C / 64) decides the route (kad_route.h route_schedule, executed by kad_kernels.hip's launchers; kad_explain.hip
+launch_explain); each boundary below is run on both of its sides, and the route is asserted from the
+library's own reporting (snapshot_paths, path_counts, last_route):
 
   nch 1..4 (C <= 256)          schedule_lean_kernel<1..4, clean>; <4, true, SM_LEAST> for C2's profile
   nch 4 -> 5 (C 256 -> 257)    lean -> schedule_wide_kernel, on clean snapshots
@@ -35,9 +35,9 @@ from kubeadmiral_amd import types as T
 
 pytestmark = pytest.mark.gpu
 
-ROW_MAX_C = 12288       # kad_kernels.hip
+ROW_MAX_C = 12288       # kad_layout.h
 FITFOLD_MAX_C = 16384   # kad_device.h
-WIDE_P = 512            # kad_device.h
+WIDE_P = 512            # kad_layout.h
 LEAN_P = 256            # schedule_lean_kernel<0>: 64 * LEAN_QMAX_DYN register positions
 
 
@@ -74,6 +74,7 @@ def assert_clean_route(ctx, C, W, klass="strict"):
     paths, counts = ctx.snapshot_paths(), ctx.path_counts()
     assert paths["resource_class"] == klass, paths
     assert paths["wide"] == (5 <= nch_of(C) <= 16), paths
+    assert (ctx.last_route()["family"] == "WIDE") == paths["wide"], ctx.last_route()
     assert paths["fitfold"] == (C <= FITFOLD_MAX_C), paths
     assert counts["units"] == W, counts
     return paths, counts
@@ -144,6 +145,10 @@ def test_specialised_instantiations(ctx, case, prof, C, zero, relaxed):
     assert nch_of(C) == {"c3": 16, "default": 8, "c2": 4}[prof]
     least = 1 << F.PLUGIN_ID[F.ClusterResourcesLeastAllocated]
     assert (fwk.to_c().score_mask == least) == (prof != "default")
+    want_variant = {"c3": "WIDE_LEAST", "default": "WIDE8_DEFAULT", "c2": "LEAN4_CLEAN_LEAST"}[prof]
+    if zero and prof != "c2":
+        want_variant += "_ZR"  # schedule_wide_kernel<..., true>
+    assert ctx.last_route()["variant"] == want_variant, ctx.last_route()
     assert_same(got, want, f"{prof} C={C} zero={zero} relaxed={relaxed}")
 
 
