@@ -60,6 +60,7 @@ extern "C" {
 #define KAD_ESTATE -4       /* e.g. schedule before snapshot/batch upload   */
 #define KAD_EUNSUPPORTED -5 /* plugin not in the in-tree set (webhook)      */
 #define KAD_EHOST -6        /* other host-side failure (e.g. a pool thread could not start) */
+#define KAD_ENOSPC -7       /* kad_follower_union: out_capacity is less than the ids to emit */
 
 /* ------------------------------------------------------------- plugins
  * In-tree plugin ids = bit positions in kad_profile masks.
@@ -589,6 +590,95 @@ int kad_override_match(kad_ctx* ctx, const kad_override_batch* batch, const kad_
 /* Device time of the last kad_override_match that launched, from HIP events: ms[0] = the set's requirement
  * rows, ms[1] = the rule rows, ms[2] = the status + match kernels. No reference counterpart. */
 int kad_override_timing(kad_ctx* ctx, float ms[3]);
+
+/* ------------------------------------------------------ follower scheduling
+ * The third consumer of the placements is the follower controller (pkg/controllers/follower/controller.go):
+ * for every ConfigMap, Secret, PVC, ServiceAccount, Service and Ingress that workloads reference
+ * (supportedFollowerTypes, controller.go:80-87) it sets the follower's placement to the union of
+ * ClusterNameUnion() (pkg/apis/types/v1alpha1/extensions_placements.go:24-33) over its leaders
+ * (updateFollower / leaderPlacementUnion, controller.go:380-421, 532-550) through SetPlacementNames
+ * (extensions_placements.go:78-103), whose hasChange decides whether the follower object is updated.
+ * kad_follower_union computes, for a batch of followers, that union, hasChange against the placement the
+ * follower holds now, and the union's members in ascending id order for the followers that change.
+ *
+ * Id space: n_ids cluster ids — the resident snapshot's C clusters (id = snapshot position) followed by names
+ * the caller interned itself, because a leader may still hold a placement on a cluster that left the snapshot
+ * and the reference unions it by name. C <= n_ids <= 131072, else KAD_EINVAL. -1 is not an id here.
+ *
+ * Leaders, n_leaders of them; a leader's set is ClusterNameUnion() of the object as it stands after this
+ * reconcile:
+ *   explicit (lead_off != NULL): lead_off[n_leaders + 1] / lead_cluster, any order, duplicates allowed;
+ *   resident (lead_off == NULL): leader i < W is unit i of the last kad_schedule (KAD_ESTATE if nothing was
+ *     scheduled; W = the resident batch's units, n_leaders >= W, leaders from W on have only keep_* entries).
+ *     The slot rules are kad_override_match's: status KAD_ST_OK gives the unit's count output slots,
+ *     KAD_ST_STICKY its KAD_B_CUR_ID entries (current clusters outside the snapshot are not in that array:
+ *     the caller, who holds the names, passes them in keep_*), KAD_ST_NO_FEASIBLE nothing. For a unit whose
+ *     status is an error class nothing is applied to the object (scheduler.go:505-517), so the leader keeps
+ *     its current scheduler placement: sched_off[W + 1] / sched_cluster (NULL: none), the CSR
+ *     kad_result_state.place_* describes, read ONLY for error-status units.
+ *   keep_off[n_leaders + 1] / keep_cluster (NULL: empty), both modes: always unioned in — the placements other
+ *     controllers keep on the leader object.
+ * Followers, n_followers of them: fol_off[F + 1] / fol_leader are indices into the leaders; -1 is a leader
+ * absent from the store, skipped (controller.go:541-543); a leader may repeat. cur_off[F + 1] / cur_cluster
+ * are the follower-controller placement the follower object holds now (duplicates allowed) and cur_has[F]
+ * says whether that placement entry exists; cur_has[i] = 0 with a non-empty range is KAD_EINVAL (an entry that
+ * does not exist holds no clusters; an entry that exists may be empty).
+ *
+ * Outputs: changed[F] is exactly SetPlacementNames' hasChange — an empty union gives cur_has
+ * (DeletePlacement), otherwise inequality of the union and cur_cluster as sets; count[F] = |union|;
+ * out_off[F + 1] and out_cluster hold the union in ascending id order for changed followers only (unchanged
+ * ones occupy zero slots), or for every follower with KAD_FOL_EMIT_ALL; the offsets come from a device scan.
+ * out_cluster has out_capacity elements: if out_off[F] exceeds it the call returns KAD_ENOSPC with nothing
+ * written to out_cluster and changed / count / out_off valid, and the caller retries with out_off[F] slots.
+ *
+ * Every offset array (monotone from 0), id and leader index is validated on the host before anything is
+ * launched (KAD_EINVAL). Runs on the ctx stream (follower_union_*_kernel, the offset scan,
+ * follower_emit_*_kernel: kad_follower.hip); blocks until the outputs are in the caller's buffers. Leaves the
+ * last results, the timings and any later kad_schedule as they were, like kad_explain. A kad_group member
+ * accepts explicit mode only: resident mode there is KAD_EUNSUPPORTED, because a follower's leaders may live
+ * in other members' shards. */
+#define KAD_FOL_EMIT_ALL 1u
+typedef struct kad_follower_batch {
+  int32_t n_ids;
+  int32_t n_leaders;
+  int32_t n_followers; /* F */
+  uint32_t flags;      /* KAD_FOL_* */
+  const int32_t* lead_off;      /* [n_leaders + 1] or NULL (resident mode) */
+  const int32_t* lead_cluster;  /* [lead_off[n_leaders]] */
+  const int32_t* sched_off;     /* resident mode: [W + 1] or NULL */
+  const int32_t* sched_cluster; /* [sched_off[W]] */
+  const int32_t* keep_off;      /* [n_leaders + 1] or NULL */
+  const int32_t* keep_cluster;  /* [keep_off[n_leaders]] */
+  const int32_t* fol_off;       /* [F + 1] */
+  const int32_t* fol_leader;    /* [fol_off[F]] */
+  const int32_t* cur_off;       /* [F + 1] */
+  const int32_t* cur_cluster;   /* [cur_off[F]] */
+  const uint8_t* cur_has;       /* [F] */
+  int64_t out_capacity;         /* elements of out_cluster */
+} kad_follower_batch;
+typedef struct kad_follower_view {
+  uint8_t* changed;     /* [F] */
+  int32_t* count;       /* [F] */
+  int64_t* out_off;     /* [F + 1] */
+  int32_t* out_cluster; /* [out_capacity]; may be NULL at capacity 0 */
+} kad_follower_view;
+int kad_follower_union(kad_ctx* ctx, const kad_follower_batch* batch, const kad_follower_view* out);
+/* Host only (no device, no ctx): the same validation against a snapshot of n_clusters clusters and, for a
+ * resident-mode batch, a resident batch of n_units units (n_units < 0: nothing scheduled, KAD_ESTATE). */
+int kad_follower_check(const kad_follower_batch* batch, const kad_follower_view* out, int32_t n_clusters,
+                       int32_t n_units);
+/* Device time of the last kad_follower_union that launched (n_followers > 0), from HIP events: ms[0] = the
+ * union / compare kernel, ms[1] = the offset scan + the emit kernel. No reference counterpart. */
+int kad_follower_timing(kad_ctx* ctx, float ms[2]);
+/* What a kad_follower_union launches, as the library's one decision computes it (csrc/kad_follower.h
+ * route_follower; no device work, no ctx): out[KAD_FOL_ROUTE_FIELDS] is [0] path (0: one follower per wave
+ * at a time, n_ids <= 8192; 1: one per 256-thread block), [1] u32 words per bitmap, [2] block threads,
+ * [3] grid of the union and the emit kernel, [4] static LDS bytes per block, [5] the distance between two
+ * consecutive followers of one wave (path 0) or block (path 1). kad_follower_last_route: the same record for
+ * the last kad_follower_union that launched (KAD_ESTATE before one). Measurement / tests only. */
+#define KAD_FOL_ROUTE_FIELDS 6
+int kad_follower_route_eval(int32_t n_ids, int32_t n_followers, int32_t n_cu, int32_t* out);
+int kad_follower_last_route(kad_ctx* ctx, int32_t* out);
 
 /* ------------------------------------------------ result application (§8 f3)
  * applySchedulingResult (pkg/controllers/scheduler/scheduler.go:632-695) writes a unit's result into its

@@ -60,6 +60,7 @@ class BatchReconciler:
         self.hasher = TriggerHasher(self.ctx)
         self.scheduler = BatchScheduler(self.ctx)
         self._clusters_key = None
+        self._pass = None  # the batch the last reconcile left resident (last_pass)
 
     def _framework(self, profile: Optional[dict]) -> F.Framework:
         """createFramework (scheduler.go:492, profile.go:52-82): default plugins + the profile's changes."""
@@ -81,6 +82,7 @@ class BatchReconciler:
         (``FilterDiagnosis.message``), from one kad_explain per framework batch over just those units.
         """
         profiles = profiles or {}
+        self._pass = None
         out: List[Optional[ReconcileOutcome]] = [None] * len(objs)
         why: Dict[int, str] = {}
         ctx_pol: List[Optional[O.PropagationPolicy]] = [None] * len(objs)
@@ -248,6 +250,7 @@ class BatchReconciler:
                 continue
             res, snap = self.scheduler.schedule_columns(fwk, built.cols, clusters)
             names = snap.names
+            self._record_pass(len(res.status), ok, out)
             if why is not None:
                 self._explain(fwk, [(i, w) for i, w in ok if int(res.status[w]) == ST_NO_FEASIBLE], why)
             for i, w in ok:
@@ -295,6 +298,92 @@ class BatchReconciler:
             out[i] = ReconcileOutcome(STATUS_ALL_OK, "scheduled", True, bool(modified[k]), r,
                                       diagnosis=(why or {}).get(i, ""))
 
+    # ------------------------------------------------------------------ follower scheduling
+    def _record_pass(self, n_units: int, ok: List[Tuple[int, int]], out: list) -> None:
+        """The batch now resident on the device: (its unit count, (object index, unit) pairs, the outcome list
+        the reconcile goes on filling in) — what :attr:`last_pass` is computed from."""
+        self._pass = (n_units, list(ok), out)
+
+    @property
+    def last_pass(self) -> Optional[List[int]]:
+        """What :meth:`reconcile_followers` takes as ``resident`` after the last :meth:`reconcile` /
+        :meth:`reconcile_texts`: per unit w of the batch that pass left resident on the device, the index (in
+        the reconciled sequence) of the object whose scheduler placement that unit's device result describes,
+        -1 for none; None when the pass scheduled nothing (whatever is resident belongs to an earlier pass).
+        A unit describes its object when the result was applied (stage ``scheduled``) or when Schedule failed
+        (``schedule-error``: the device status is an error class, for which the follower union reads the
+        placement the object keeps). Objects whose apply failed keep their old placement although their unit
+        is OK on the device: they are left out, and read from their dicts like every leader outside the batch."""
+        if self._pass is None:
+            return None
+        n_units, ok, out = self._pass
+        units = [-1] * n_units
+        for i, w in ok:
+            if out[i] is not None and out[i].stage in ("scheduled", "schedule-error"):
+                units[w] = i
+        return units
+
+    def reconcile_followers(self, leaders: Sequence[dict], followers: Sequence[dict],
+                            clusters: List[T.FederatedCluster], resident: Optional[Sequence[int]] = None,
+                            source_to_federated=None):
+        """The follower controller's two reconciles for a batch (pkg/controllers/follower/controller.go):
+        every leader's followers are inferred (reconcileLeader :285-311), then every follower dict gets
+        ``spec.follows`` and the union of its leaders' placements (reconcileFollower :463-483, updateFollower),
+        in place, with the unions and SetPlacementNames' change test in one kad_follower_union.
+
+        ``leaders``: federated leader dicts as they stand after their own reconcile. ``resident``:
+        ``self.last_pass`` of the :meth:`reconcile` / :meth:`reconcile_texts` just run over the same sequence —
+        those leaders' scheduler placements are then read from the results still on the device (resident
+        mode: OK and sticky units from their slots, error units from the placement the object keeps), the
+        other leaders' and every other controller's placements from the dicts; None: every placement from the
+        dicts (explicit mode). Returns (needs_update per follower, {leader index: error} for the leaders whose
+        followers could not be inferred — they contribute no followers, as a reconcile that ends in
+        StatusError leaves the cache)."""
+        from . import follower as FL
+
+        s2f = source_to_federated if source_to_federated is not None else FL.default_source_to_federated()
+        index = FL.FollowerIndex()
+        errors: Dict[int, str] = {}
+        refs = [FL.leader_reference(ld) for ld in leaders]
+        for i, ld in enumerate(leaders):
+            try:
+                index.update_leader(refs[i], FL.infer_followers(ld, FL.source_group_kind(ld), s2f))
+            except FL.FollowerError as e:
+                errors[i] = str(e)
+        frefs = [FL.follower_reference(f) for f in followers]
+        for fr, f in zip(frefs, followers):
+            index.observe_follower(fr, f)
+        if resident is None:
+            snap = self.scheduler.set_clusters(clusters)
+            order = list(range(len(leaders)))
+            args = {"leaders": [FL.placement_names(leaders[i]) for i in order]}
+        else:
+            snap = self.ctx.snap  # the snapshot the resident batch was scheduled against
+            W = len(resident)
+            rest = sorted(set(range(len(leaders))) - set(resident))
+            order = list(resident) + rest
+            sched_name = O.PREFIXED_GLOBAL_SCHEDULER_NAME
+            keep, sched = [], []
+            for k, i in enumerate(order):
+                if i < 0:
+                    names = own = []
+                elif k < W:
+                    own = FL.placement_names(leaders[i], sched_name) or []
+                    # the device reads the unit's result; it lacks what other controllers placed and, for a
+                    # sticky unit, the current clusters that left the snapshot
+                    names = FL.placement_names(leaders[i], None, exclude=sched_name) + \
+                        [n for n in own if n not in snap.name_id]
+                else:
+                    own, names = [], FL.placement_names(leaders[i])
+                keep.append(names)
+                if k < W:
+                    sched.append(own)
+            args = {"leaders": None, "keep": keep, "sched": sched, "n_leaders": len(order)}
+        leader_index = {refs[i]: k for k, i in enumerate(order) if i >= 0}
+        fol_off, fol_leader, desired = index.csr(frefs, leader_index)
+        placer = FL.FollowerPlacer(self.ctx, snap)
+        return placer.apply(followers, desired, fol_off, fol_leader, **args), errors
+
     # ------------------------------------------------------------------ the reconcile over JSON texts
     def reconcile_texts(self, texts: Sequence, policies: Sequence, clusters: List[T.FederatedCluster],
                         profiles: Optional[Dict[str, Optional[dict]]] = None
@@ -314,6 +403,7 @@ class BatchReconciler:
         from .results import to_schedule_result_cols
 
         profiles = profiles or {}
+        self._pass = None
         ot, pt = K._texts(texts), K._texts(policies)
         n = len(ot)
         out: List[Optional[ReconcileOutcome]] = [None] * n
@@ -412,6 +502,7 @@ class BatchReconciler:
                 continue
             res, snap = self.scheduler.schedule_columns(fwk, built.cols, clusters)
             names = snap.names
+            self._record_pass(len(res.status), ok, out)
             for i, w in ok:
                 r = to_schedule_result_cols(res, w, built.cols, names)
                 if isinstance(r, T.ScheduleError):

@@ -14,6 +14,7 @@
 
 #include "../../include/kad_sched.h"
 #include "kad_device.h"
+#include "kad_follower.h"
 #include "kad_pool.h"
 
 using namespace kad;
@@ -105,6 +106,13 @@ struct kad_ctx {
   hipEvent_t oev[4] = {nullptr, nullptr, nullptr, nullptr};  // start, after requirement rows, after rule rows, end
   bool ovr_ran = false;       // oev hold a kad_override_match run
   int32_t cur_lo = 0, cur_n = 0;  // the resident batch's (shard's) range of KAD_B_CUR_ID entries
+  // follower scheduling (kad_follower_union): one call's inputs and outputs
+  void* d_fol = nullptr;
+  size_t fol_cap = 0;
+  hipEvent_t fev[3] = {nullptr, nullptr, nullptr};  // start, after the union kernel, after scan + emit
+  bool fol_ran = false;        // fev hold a kad_follower_union run
+  FollowerRoute fol_route{};   // what it launched (kad_follower_last_route)
+  bool group_member = false;   // owned by a kad_group: its resident results are a shard's
   // HIP event records around the stages (kad_set_timing); timed = the last
   // kad_schedule recorded them
   bool timing = false, timed = false;
@@ -477,6 +485,11 @@ int kad_ctx_create(int hip_device, kad_ctx** out) {
       kad_ctx_destroy(c);
       return KAD_EHIP;
     }
+  for (auto& e : c->fev)
+    if (hipEventCreate(&e) != hipSuccess) {
+      kad_ctx_destroy(c);
+      return KAD_EHIP;
+    }
   *out = c;
   return KAD_OK;
 }
@@ -489,7 +502,7 @@ int kad_ctx_destroy(kad_ctx* c) {
   for (void* p : {c->d_snap, c->d_batch, (void*)c->d_plan_rows, c->d_plan_hdr, c->d_plan_big, (void*)c->d_req_mask, (void*)c->d_status, (void*)c->d_count,
                   (void*)c->d_cluster, (void*)c->d_flags, (void*)c->d_replicas, c->d_scratch, c->d_rec, c->d_delta, c->d_sw, c->d_cw, c->d_defer, c->d_wq, c->d_slices, c->d_fit, c->d_reqseg, c->d_rowslab, c->d_vrows, c->d_rescols,
                   c->t_suffix, c->t_prefix, c->t_work, c->t_tabs, c->d_diff, c->d_explain, c->d_ovr, c->d_ovr_reqseg,
-                  c->d_ovr_rows, c->d_ovr_work})
+                  c->d_ovr_rows, c->d_ovr_work, c->d_fol})
     if (p) (void)hipFree(p);
   for (auto& e : c->ev)
     if (e) (void)hipEventDestroy(e);
@@ -498,6 +511,8 @@ int kad_ctx_destroy(kad_ctx* c) {
   for (auto& e : c->xev)
     if (e) (void)hipEventDestroy(e);
   for (auto& e : c->oev)
+    if (e) (void)hipEventDestroy(e);
+  for (auto& e : c->fev)
     if (e) (void)hipEventDestroy(e);
   if (c->side) {
     (void)hipStreamSynchronize(c->side);
@@ -2078,6 +2093,200 @@ int kad_override_timing(kad_ctx* c, float ms[3]) {
   return KAD_OK;
 }
 
+// ------------------------------------------------------ follower scheduling
+// Every offset array monotone from 0, every id in [0, n_ids), every leader index in [-1, n_leaders): all of
+// it on the host, before anything is copied or launched. C = the snapshot's clusters; W = the resident
+// units a resident-mode batch reads (ignored in explicit mode).
+static int validate_follower(const kad_follower_batch* b, const kad_follower_view* out, int C, int64_t W,
+                             std::string* err) {
+  auto bad = [&](const char* m) {
+    *err = m;
+    return KAD_EINVAL;
+  };
+  const int64_t n_ids = b->n_ids, L = b->n_leaders, F = b->n_followers;
+  if (n_ids < C || n_ids > FOL_MAX_IDS) return bad("n_ids must lie in [the snapshot's clusters, 131072]");
+  if (L < 0 || F < 0 || b->out_capacity < 0) return bad("negative count or capacity");
+  if (b->flags & ~(uint32_t)KAD_FOL_EMIT_ALL) return bad("unknown flag");
+  // a CSR of n rows whose entries lie in [lo, hi)
+  auto csr_bad = [&](const int32_t* off, const int32_t* data, int64_t n, int64_t lo, int64_t hi) {
+    if (!off || off[0] != 0) return true;
+    if (first_bad(n, [&](int64_t i) { return off[i + 1] < off[i]; }) >= 0) return true;
+    const int64_t m = off[n];
+    if (m && !data) return true;
+    return first_bad(m, [&](int64_t j) { return data[j] < lo || data[j] >= hi; }) >= 0;
+  };
+  const bool resident = b->lead_off == nullptr;
+  if (!resident) {
+    if (csr_bad(b->lead_off, b->lead_cluster, L, 0, n_ids)) return bad("lead_off / lead_cluster malformed or id out of range");
+  } else {
+    if (L < W) return bad("resident mode: n_leaders is less than the resident batch's units");
+    if (b->sched_off && csr_bad(b->sched_off, b->sched_cluster, W, 0, n_ids))
+      return bad("sched_off / sched_cluster malformed or id out of range");
+  }
+  if (b->keep_off && csr_bad(b->keep_off, b->keep_cluster, L, 0, n_ids))
+    return bad("keep_off / keep_cluster malformed or id out of range");
+  if (csr_bad(b->fol_off, b->fol_leader, F, -1, L)) return bad("fol_off / fol_leader malformed or leader index out of range");
+  if (csr_bad(b->cur_off, b->cur_cluster, F, 0, n_ids)) return bad("cur_off / cur_cluster malformed or id out of range");
+  if (F && !b->cur_has) return bad("cur_has missing");
+  {
+    const int32_t* co = b->cur_off;
+    const uint8_t* ch = b->cur_has;
+    if (first_bad(F, [&](int64_t i) { return !ch[i] && co[i + 1] > co[i]; }) >= 0)
+      return bad("cur_has = 0 with a non-empty cur range: a placement entry that does not exist holds no clusters");
+  }
+  if (!out || !out->out_off || (F && (!out->changed || !out->count)) || (b->out_capacity && !out->out_cluster))
+    return bad("output view missing");
+  return KAD_OK;
+}
+
+static int follower_union_locked(kad_ctx* c, const kad_follower_batch* b, const kad_follower_view* out) {
+  if (!c->have_snapshot) return fail(c, KAD_ESTATE, "a snapshot must be uploaded first");
+  const bool resident = b->lead_off == nullptr;
+  if (resident && c->group_member)
+    return fail(c, KAD_EUNSUPPORTED, "resident mode on a kad_group member: a follower's leaders may live in other shards");
+  if (resident && (!c->have_batch || !c->ran)) return fail(c, KAD_ESTATE, "nothing has been scheduled");
+  const int64_t W = resident ? c->unit_n : 0;
+  std::string err;
+  if (int r = validate_follower(b, out, c->sd.C, W, &err)) return fail(c, r, err);
+  const int F = b->n_followers, L = b->n_leaders;
+  out->out_off[0] = 0;
+  if (F == 0) return KAD_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const FollowerRoute route = route_follower(b->n_ids, F, n_cus());
+  // one buffer: the inputs, then changed / count / out_off / the scan's block sums / out_cluster
+  struct Part {
+    const void* h;
+    size_t bytes, at;
+  };
+  auto a256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  size_t total = 0;
+  auto part = [&](const void* h, size_t bytes) {
+    Part p{h, bytes, total};
+    total += a256(bytes ? bytes : 4);
+    return p;
+  };
+  const size_t n_lead = resident ? 0 : (size_t)b->lead_off[L], n_sched = resident && b->sched_off ? (size_t)b->sched_off[W] : 0,
+               n_keep = b->keep_off ? (size_t)b->keep_off[L] : 0, n_fl = (size_t)b->fol_off[F], n_cur = (size_t)b->cur_off[F];
+  const Part p_lo = part(b->lead_off, resident ? 0 : 4 * ((size_t)L + 1)), p_lc = part(b->lead_cluster, 4 * n_lead),
+             p_so = part(resident ? b->sched_off : nullptr, resident && b->sched_off ? 4 * ((size_t)W + 1) : 0),
+             p_sc = part(b->sched_cluster, 4 * n_sched), p_ko = part(b->keep_off, b->keep_off ? 4 * ((size_t)L + 1) : 0),
+             p_kc = part(b->keep_cluster, 4 * n_keep), p_fo = part(b->fol_off, 4 * ((size_t)F + 1)),
+             p_fl = part(b->fol_leader, 4 * n_fl), p_co = part(b->cur_off, 4 * ((size_t)F + 1)),
+             p_cc = part(b->cur_cluster, 4 * n_cur), p_ch = part(b->cur_has, (size_t)F);
+  const size_t scan_blocks = ((size_t)F + 256 * FOL_SCAN_ITEMS - 1) / (256 * FOL_SCAN_ITEMS);
+  const Part o_changed = part(nullptr, (size_t)F), o_count = part(nullptr, 4 * (size_t)F),
+             o_off = part(nullptr, 8 * ((size_t)F + 1)), o_sums = part(nullptr, 8 * scan_blocks),
+             o_cluster = part(nullptr, 4 * (size_t)b->out_capacity);
+  if (int r = grow(c, &c->d_fol, &c->fol_cap, total)) return r;
+  char* d = static_cast<char*>(c->d_fol);
+  for (const Part* p : {&p_lo, &p_lc, &p_so, &p_sc, &p_ko, &p_kc, &p_fo, &p_fl, &p_co, &p_cc, &p_ch})
+    if (p->h && p->bytes) HIPCHK(c, hipMemcpyAsync(d + p->at, p->h, p->bytes, hipMemcpyHostToDevice, c->stream));
+  auto i32 = [&](const Part& p) { return p.h ? reinterpret_cast<const int32_t*>(d + p.at) : nullptr; };
+  FollowerDev fd{};
+  fd.n_ids = b->n_ids;
+  fd.nw = route.words;
+  fd.F = F;
+  fd.n_leaders = L;
+  fd.lead_off = i32(p_lo);
+  fd.lead_cluster = reinterpret_cast<const int32_t*>(d + p_lc.at);
+  fd.resident = resident ? 1 : 0;
+  fd.W = (int)W;
+  if (resident) {
+    fd.out_off = c->bd.out_off;
+    fd.cur_off = c->bd.cur_off;
+    fd.cur_id = c->bd.cur_id;
+    fd.res_status = c->d_status;
+    fd.res_count = c->d_count;
+    fd.res_cluster = c->d_cluster;
+    fd.slot_lo = c->slot_lo;
+  }
+  fd.sched_off = i32(p_so);
+  fd.sched_cluster = reinterpret_cast<const int32_t*>(d + p_sc.at);
+  fd.keep_off = i32(p_ko);
+  fd.keep_cluster = reinterpret_cast<const int32_t*>(d + p_kc.at);
+  fd.fol_off = i32(p_fo);
+  fd.fol_leader = reinterpret_cast<const int32_t*>(d + p_fl.at);
+  fd.fcur_off = i32(p_co);
+  fd.fcur_cluster = reinterpret_cast<const int32_t*>(d + p_cc.at);
+  fd.fcur_has = reinterpret_cast<const uint8_t*>(d + p_ch.at);
+  fd.emit_all = (b->flags & KAD_FOL_EMIT_ALL) ? 1 : 0;
+  fd.capacity = b->out_capacity;
+  fd.changed = reinterpret_cast<uint8_t*>(d + o_changed.at);
+  fd.count = reinterpret_cast<int32_t*>(d + o_count.at);
+  fd.fout_off = reinterpret_cast<int64_t*>(d + o_off.at);
+  fd.scan_sums = reinterpret_cast<int64_t*>(d + o_sums.at);
+  fd.out_cluster = reinterpret_cast<int32_t*>(d + o_cluster.at);
+  HIPCHK(c, hipEventRecord(c->fev[0], c->stream));
+  HIPCHK(c, launch_follower_union(fd, route, c->stream));
+  HIPCHK(c, hipEventRecord(c->fev[1], c->stream));
+  HIPCHK(c, launch_follower_scan(fd, c->stream));
+  HIPCHK(c, launch_follower_emit(fd, route, c->stream));
+  HIPCHK(c, hipEventRecord(c->fev[2], c->stream));
+  c->fol_ran = true;
+  c->fol_route = route;
+  HIPCHK(c, hipMemcpyAsync(out->changed, fd.changed, (size_t)F, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(out->count, fd.count, 4 * (size_t)F, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(out->out_off, fd.fout_off, 8 * ((size_t)F + 1), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const int64_t n_out = out->out_off[F];
+  if (n_out > b->out_capacity)
+    return fail(c, KAD_ENOSPC, "out_capacity " + std::to_string(b->out_capacity) + " < " + std::to_string(n_out) +
+                                   " emitted ids: retry with out_off[n_followers] slots");
+  if (n_out) {
+    HIPCHK(c, hipMemcpyAsync(out->out_cluster, fd.out_cluster, 4 * (size_t)n_out, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  return KAD_OK;
+}
+
+int kad_follower_check(const kad_follower_batch* b, const kad_follower_view* out, int32_t n_clusters, int32_t n_units) {
+  try {
+    if (!b || n_clusters < 0) return KAD_EINVAL;
+    if (!b->lead_off && n_units < 0) return KAD_ESTATE;
+    std::string err;
+    return validate_follower(b, out, n_clusters, b->lead_off ? 0 : n_units, &err);
+  } catch (...) {
+    return KAD_EHOST;
+  }
+}
+
+int kad_follower_union(kad_ctx* c, const kad_follower_batch* b, const kad_follower_view* out) {
+  return guarded(c, [&]() -> int {
+    if (!c || !b) return KAD_EINVAL;
+    std::lock_guard<std::mutex> g(c->mu);
+    return follower_union_locked(c, b, out);
+  });
+}
+
+int kad_follower_timing(kad_ctx* c, float ms[2]) {
+  return guarded(c, [&]() -> int {
+    if (!c || !ms) return KAD_EINVAL;
+    std::lock_guard<std::mutex> g(c->mu);
+    if (!c->fol_ran) return fail(c, KAD_ESTATE, "no kad_follower_union ran");
+    HIPCHK(c, hipEventSynchronize(c->fev[2]));
+    for (int i = 0; i < 2; i++) HIPCHK(c, hipEventElapsedTime(&ms[i], c->fev[i], c->fev[i + 1]));
+    return KAD_OK;
+  });
+}
+
+int kad_follower_route_eval(int32_t n_ids, int32_t n_followers, int32_t n_cu, int32_t* out) {
+  if (!out || n_ids < 0 || n_ids > FOL_MAX_IDS || n_followers < 0 || n_cu < 1) return KAD_EINVAL;
+  const FollowerRoute r = route_follower(n_ids, n_followers, n_cu);
+  static_assert(sizeof r == 4 * KAD_FOL_ROUTE_FIELDS, "kad_follower_route_eval's record");
+  memcpy(out, &r, sizeof r);
+  return KAD_OK;
+}
+
+int kad_follower_last_route(kad_ctx* c, int32_t* out) {
+  return guarded(c, [&]() -> int {
+    if (!c || !out) return KAD_EINVAL;
+    std::lock_guard<std::mutex> g(c->mu);
+    if (!c->fol_ran) return fail(c, KAD_ESTATE, "no kad_follower_union ran");
+    memcpy(out, &c->fol_route, sizeof c->fol_route);
+    return KAD_OK;
+  });
+}
+
 int kad_select_rows(kad_ctx* c, int n_rows, const int32_t* row_off, const int64_t* scores, const int64_t* maxc,
                     uint32_t pflags, int32_t* out_count, int32_t* out_sel, int32_t* out_status) {
   return guarded(c, [&]() -> int {
@@ -2397,6 +2606,7 @@ int kad_group_create(const int* hip_devices, int n, kad_group** out) {
       kad_group_destroy(g);
       return r;
     }
+    c->group_member = true;
     g->m.push_back(c);
   }
   // direct peer access for the snapshot copies from member 0 (hipMemcpyPeerAsync works without it, staged)

@@ -28,7 +28,8 @@ LIB_PATH = os.path.join(HERE, "libkad.so")
 HEADER = os.path.join(os.path.dirname(HERE), "include", "kad_sched.h")
 
 KAD_ERRORS = {-1: "KAD_EINVAL", -2: "KAD_EHIP", -3: "KAD_ENOMEM", -4: "KAD_ESTATE", -5: "KAD_EUNSUPPORTED",
-              -6: "KAD_EHOST"}
+              -6: "KAD_EHOST", -7: "KAD_ENOSPC"}
+KAD_EINVAL, KAD_ESTATE, KAD_EUNSUPPORTED, KAD_ENOSPC = -1, -4, -5, -7
 
 
 class KadError(RuntimeError):
@@ -60,6 +61,20 @@ class OverrideBatch(ctypes.Structure):  # kad_override_batch
 
 class OverrideView(ctypes.Structure):  # kad_override_view
     _fields_ = [("status", ctypes.c_void_p), ("matched", ctypes.c_void_p)]
+
+
+class FollowerBatch(ctypes.Structure):  # kad_follower_batch
+    _fields_ = [("n_ids", ctypes.c_int32), ("n_leaders", ctypes.c_int32), ("n_followers", ctypes.c_int32),
+                ("flags", ctypes.c_uint32), ("lead_off", ctypes.c_void_p), ("lead_cluster", ctypes.c_void_p),
+                ("sched_off", ctypes.c_void_p), ("sched_cluster", ctypes.c_void_p), ("keep_off", ctypes.c_void_p),
+                ("keep_cluster", ctypes.c_void_p), ("fol_off", ctypes.c_void_p), ("fol_leader", ctypes.c_void_p),
+                ("cur_off", ctypes.c_void_p), ("cur_cluster", ctypes.c_void_p), ("cur_has", ctypes.c_void_p),
+                ("out_capacity", ctypes.c_int64)]
+
+
+class FollowerView(ctypes.Structure):  # kad_follower_view
+    _fields_ = [("changed", ctypes.c_void_p), ("count", ctypes.c_void_p), ("out_off", ctypes.c_void_p),
+                ("out_cluster", ctypes.c_void_p)]
 
 
 _lib = None
@@ -157,6 +172,12 @@ def load_library(path: str = LIB_PATH):
         L.kad_override_policies_check.argtypes = [P, SZ, P, SZ]
         L.kad_override_match.argtypes = [P, P, P]
         L.kad_override_timing.argtypes = [P, P]
+    if hasattr(L, "kad_follower_union"):
+        L.kad_follower_union.argtypes = [P, P, P]
+        L.kad_follower_check.argtypes = [P, P, ctypes.c_int32, ctypes.c_int32]
+        L.kad_follower_timing.argtypes = [P, P]
+        L.kad_follower_route_eval.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, P]
+        L.kad_follower_last_route.argtypes = [P, P]
     L.kad_debug_inject_fault.argtypes = [P, I]
     L.kad_debug_plan_force_workspace.argtypes = [P, I]
     L.kad_trigger_suffix_upload.argtypes = [P, P, SZ]
@@ -226,6 +247,62 @@ def host_array(n: int, dtype) -> np.ndarray:
 
 def _p(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+
+
+FOLLOWER_ROUTE = ("path", "words", "threads", "grid", "lds", "stride")  # kad_follower_route_eval's record
+
+
+def _follower_route_dict(out) -> dict:
+    d = dict(zip(FOLLOWER_ROUTE, out))
+    d["path"] = ("WAVE", "BLOCK")[d["path"]]
+    return d
+
+
+def follower_route_eval(n_ids: int, n_followers: int, n_cu: int = 256) -> dict:
+    """kad_follower_route_eval: the launch decision of a follower_union (needs no GPU)."""
+    out = (ctypes.c_int32 * len(FOLLOWER_ROUTE))()
+    rc = load_library().kad_follower_route_eval(n_ids, n_followers, n_cu, out)
+    if rc != 0:
+        raise ValueError(f"kad_follower_route_eval: {rc}")
+    return _follower_route_dict(out)
+
+
+def follower_args(n_ids: int, followers, leaders=None, keep=None, sched=None, n_leaders=None,
+                  emit_all: bool = False, capacity: int = 0):
+    """The kad_follower_batch / kad_follower_view of one call, with the arrays that back them.
+
+    ``followers``: (fol_off[F + 1], fol_leader[], cur_off[F + 1], cur_cluster[], cur_has[F]); ``leaders``:
+    (lead_off[n_leaders + 1], lead_cluster[]) or None for resident mode (leader i = unit i of the last
+    schedule()); ``keep`` / ``sched``: (off, ids) CSRs or None; ``n_leaders`` defaults to the rows of
+    ``leaders``, else of ``keep`` (resident mode without keep: pass it). Returns (batch, view, the int32 /
+    uint8 arrays the batch points to, the output arrays by name)."""
+    i32 = lambda a: np.ascontiguousarray(a, np.int32).reshape(-1)  # noqa: E731
+    fo, fl, co, cc = (i32(a) for a in followers[:4])
+    ch = np.ascontiguousarray(followers[4], np.uint8).reshape(-1)
+    F = len(ch)
+    pairs = [None if p is None else (i32(p[0]), i32(p[1])) for p in (leaders, sched, keep)]
+    if n_leaders is None:
+        src = pairs[0] or pairs[2]
+        if src is None:
+            raise ValueError("resident mode without keep: n_leaders is required")
+        n_leaders = len(src[0]) - 1
+    out = {"changed": np.zeros(max(1, F), np.uint8), "count": np.zeros(max(1, F), np.int32),
+           "out_off": np.zeros(F + 1, np.int64), "out_cluster": np.zeros(max(1, int(capacity)), np.int32)}
+    ptr = lambda a: a.ctypes.data if len(a) else None  # noqa: E731
+    flat = []
+    for p in pairs:
+        flat += [None, None] if p is None else [p[0].ctypes.data, ptr(p[1])]
+    b = FollowerBatch(int(n_ids), int(n_leaders), F, 1 if emit_all else 0, *flat, fo.ctypes.data, ptr(fl),
+                      co.ctypes.data, ptr(cc), ch.ctypes.data if F else None, int(capacity))
+    v = FollowerView(*(out[k].ctypes.data for k in ("changed", "count", "out_off", "out_cluster")))
+    return b, v, (fo, fl, co, cc, ch, pairs), out
+
+
+def follower_check(n_clusters: int, n_units: int, n_ids: int, followers, **kw) -> int:
+    """kad_follower_check: kad_follower_union's validation of :func:`follower_args` arguments against a snapshot
+    of ``n_clusters`` clusters and a scheduled batch of ``n_units`` units (-1: none); no GPU. Returns the code."""
+    b, v, _keepalive, _ = follower_args(n_ids, followers, **kw)
+    return load_library().kad_follower_check(ctypes.byref(b), ctypes.byref(v), n_clusters, n_units)
 
 
 class Context:
@@ -467,6 +544,42 @@ class Context:
         ms = (ctypes.c_float * 3)()
         self._chk(self.L.kad_override_timing(self.h, ms))
         return float(ms[0]), float(ms[1]), float(ms[2])
+
+    def follower_union(self, n_ids: int, followers, leaders=None, keep=None, sched=None, n_leaders=None,
+                       emit_all: bool = False, capacity: Optional[int] = None, retry: bool = True) -> dict:
+        """kad_follower_union → {changed[F], count[F], out_off[F + 1], out_cluster[out_off[F]], calls}.
+        Arguments as :func:`follower_args`. ``capacity``: elements of the first call's out_cluster (default: one
+        per current-placement entry plus one per follower); when the library answers KAD_ENOSPC the call is
+        repeated once with the out_off[F] slots it asked for (``retry=False``: the error is raised, with the
+        valid changed / count / out_off of that call in ``KadError.partial``)."""
+        F = len(followers[4])
+        cap = int(capacity) if capacity is not None else len(followers[3]) + F
+        for calls in (1, 2):
+            b, v, keepalive, out = follower_args(n_ids, followers, leaders, keep, sched, n_leaders, emit_all, cap)
+            rc = self.L.kad_follower_union(self.h, ctypes.byref(b), ctypes.byref(v))
+            if rc == KAD_ENOSPC and retry and calls == 1:
+                cap = int(out["out_off"][F])
+                continue
+            if rc != 0:
+                e = KadError(rc, self.L.kad_last_error(self.h).decode())
+                if rc == KAD_ENOSPC:
+                    e.partial = {k: out[k][:F + (k == "out_off")] for k in ("changed", "count", "out_off")}
+                raise e
+            return {"changed": out["changed"][:F], "count": out["count"][:F], "out_off": out["out_off"][:F + 1],
+                    "out_cluster": out["out_cluster"][:int(out["out_off"][F])], "calls": calls}
+
+    def follower_timing(self):
+        """kad_follower_timing: device ms of the last follower_union() — (the union / compare kernel, the offset
+        scan + the emit kernel)."""
+        ms = (ctypes.c_float * 2)()
+        self._chk(self.L.kad_follower_timing(self.h, ms))
+        return float(ms[0]), float(ms[1])
+
+    def follower_last_route(self) -> dict:
+        """kad_follower_last_route: what the last follower_union() launched (follower_route_eval's record)."""
+        out = (ctypes.c_int32 * len(FOLLOWER_ROUTE))()
+        self._chk(self.L.kad_follower_last_route(self.h, out))
+        return _follower_route_dict(out)
 
     def select_rows(self, rows: Sequence[Sequence[int]], max_clusters: Sequence[Optional[int]], flags: int = 0):
         """MaxCluster on explicit score rows → per row (status, sorted selected positions)."""

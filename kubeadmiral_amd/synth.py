@@ -1046,3 +1046,40 @@ def gen_override_policies(seed: int, clusters, n_policies: int = 40, max_rules: 
         ns = None if i % 2 == 0 else namespaces[int(rng.integers(0, len(namespaces)))]
         pols.append(OV.OverridePolicy(f"op-{seed}-{i}", ns, rules))
     return pols
+
+
+# ------------------------------------------------------------ follower scheduling (kad_follower_union)
+def gen_followers(seed: int, lead_off, lead_cluster, n_ids: int, per_leader: float = 2.0, max_leaders: int = 3,
+                  changed: float = 0.01):
+    """A synthetic follower set over leaders whose cluster sets are the CSR ``lead_off`` / ``lead_cluster``
+    (ids below ``n_ids``): ``per_leader`` followers per leader on average, each following 1..``max_leaders``
+    leaders drawn near one another (objects of one namespace). A follower's current placement is the union of
+    its leaders' sets — in another order, so unchanged — except for a fraction ``changed`` of them, which lack
+    one cluster of it or, where the union is empty, hold one stale cluster. Returns kad_follower_union's
+    follower arrays (fol_off, fol_leader, cur_off, cur_cluster, cur_has) and the changed mask."""
+    rng = np.random.default_rng([seed, 0xF011])
+    lead_off = np.asarray(lead_off, np.int64)
+    lead_cluster = np.asarray(lead_cluster, np.int32)
+    L = len(lead_off) - 1
+    F = int(round(L * per_leader))
+    n = rng.integers(1, max_leaders + 1, F).astype(np.int32)
+    fol_off = np.zeros(F + 1, np.int32)
+    fol_off[1:] = np.cumsum(n)
+    base = rng.integers(0, max(1, L), F)
+    owner = np.repeat(np.arange(F), n)
+    fol_leader = ((base[owner] + rng.integers(0, 8, len(owner))) % max(1, L)).astype(np.int32)
+    stale = rng.random(F) < changed
+    cur_off = np.zeros(F + 1, np.int32)
+    cur, has = [], np.ones(F, np.uint8)
+    for i in range(F):
+        ls = fol_leader[fol_off[i]:fol_off[i + 1]]
+        u = np.unique(np.concatenate([lead_cluster[lead_off[ld]:lead_off[ld + 1]] for ld in ls])) if L else \
+            np.zeros(0, np.int32)
+        if stale[i]:
+            u = u[1:] if len(u) else np.array([int(rng.integers(0, n_ids))], np.int32)
+        elif len(u) == 0:
+            has[i] = 0
+        cur.append(u[::-1])
+        cur_off[i + 1] = cur_off[i] + len(u)
+    cur_cluster = np.concatenate(cur).astype(np.int32) if cur else np.zeros(0, np.int32)
+    return (fol_off, fol_leader, cur_off, cur_cluster, has), stale
