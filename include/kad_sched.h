@@ -680,6 +680,103 @@ int kad_follower_timing(kad_ctx* ctx, float ms[2]);
 int kad_follower_route_eval(int32_t n_ids, int32_t n_followers, int32_t n_cu, int32_t* out);
 int kad_follower_last_route(kad_ctx* ctx, int32_t* out);
 
+/* ------------------------------------------------------ auto-migration
+ * The producer of kubeadmiral.io/auto-migration-info is the auto-migration controller
+ * (pkg/controllers/automigration/controller.go:178-378, util.go:29-64): for every object that carries the
+ * scheduler's pod-unschedulable-threshold annotation it walks the pods of every member cluster, counts those
+ * that have been unschedulable for longer than the threshold, and writes the clusters whose estimated capacity
+ * falls short of the desired replicas. kad_migrate_estimate does that for a batch of objects.
+ *
+ * Times are int64 Unix nanoseconds. The batch carries ONE now_ns (the reference calls time.Now() per
+ * cluster: a declared deviation). 0 <= now_ns <= 2^61, |obj_threshold_ns| <= 2^61 and |pod_t_ns| <= 2^61, else
+ * KAD_EINVAL: then (t + threshold) - now cannot overflow and Go's saturating Time.Sub never engages.
+ *
+ * Objects, n_objects of them (only objects with a parseable threshold annotation; the disabled case,
+ * controller.go:217-224, stays with the caller): obj_seg_off[O + 1] are the object's segments, one per member
+ * cluster object (controller.go:303), obj_threshold_ns[O] the threshold.
+ * Segments, n_segments: seg_cluster[S] is an id of the kad_follower_union id space (the snapshot's C clusters,
+ * then names the caller interned; C <= n_ids <= 131072), strictly ascending within an object; seg_desired[S]
+ * is getDesiredReplicas (controller.go:406-415); seg_pod_off[S + 1] the segment's pods (at most 2^31 - 1).
+ * seg_flags[S]: KAD_MIG_SEG_SKIP for a segment the reference leaves before it counts — totalReplicas ==
+ * readyReplicas with no error (:310-314), getDesiredReplicas failed (:316-320), the pod listing failed
+ * (:323-330) — which contributes no entry and nothing to retry_after, and whose pods, if any, are not read;
+ * KAD_MIG_SEG_BACKOFF (only with SKIP) when the listing failed with clusterNeedsBackoff.
+ * Pods, n_pods: pod_t_ns[P] is lastTransitionTime of the first PodScheduled condition; pod_flags[P]:
+ * KAD_MIG_POD_DELETING (a deletion timestamp: skipped, util.go:35-37, but counted in len(pods)),
+ * KAD_MIG_POD_UNSCHED (that condition exists with Status False and Reason Unschedulable, util.go:47-51),
+ * KAD_MIG_POD_TZERO (lastTransitionTime absent or null: Go's zero time, which Unix nanoseconds cannot hold;
+ * the pod always counts as crossed and pod_t_ns is not read).
+ * The existing annotation: old_off[O + 1] / old_cluster (strictly ascending within an object) / old_cap, n_old
+ * = old_off[O] entries; an annotation that is absent, null, or does not unmarshal (:239-245) is an empty range.
+ *
+ * Outputs, per segment: uns[S] = the unschedulable count, next_cross[S] = nextCrossIn (INT64_MAX: none), cap[S]
+ * = the estimated capacity written for the cluster (-1: no entry; n >= desired ? n - uns : desired - uns, no
+ * entry at cap >= desired, clamped at 0, controller.go:345-366); a skipped segment gives 0, INT64_MAX, -1. Per
+ * object: n_written[O] entries, retry_after[O] = the minimum next_cross (INT64_MAX: none), backoff[O] (the
+ * worker result is nil iff neither, :369-377), and changed[O] = !equality.Semantic.DeepEqual(existing, new)
+ * (:247; nil and empty maps are equal).
+ *
+ * Every offset array (monotone from 0, ending at its count), id, ascending rule, flag and time is validated on
+ * the host before anything is launched (KAD_EINVAL). Runs on the ctx stream (migrate_segment_kernel,
+ * migrate_object_kernel: kad_migrate.hip); blocks until the outputs are in the caller's buffers. Needs a
+ * snapshot only for C; reads no resident state, so a kad_group member accepts it. Leaves the last results,
+ * the timings and any later kad_schedule as they were, like kad_explain. n_objects == 0 returns 0 without
+ * launching. */
+#define KAD_MIG_SEG_SKIP 1u
+#define KAD_MIG_SEG_BACKOFF 2u
+#define KAD_MIG_POD_DELETING 1u
+#define KAD_MIG_POD_UNSCHED 2u
+#define KAD_MIG_POD_TZERO 4u
+#define KAD_MIG_TIME_MAX (1ll << 61)
+typedef struct kad_migrate_batch {
+  int32_t n_ids;
+  int32_t n_objects;  /* O */
+  int32_t n_segments; /* S */
+  int32_t n_old;      /* entries of the existing annotations = old_off[O] */
+  int64_t n_pods;     /* P */
+  int64_t now_ns;
+  const int32_t* obj_seg_off;      /* [O + 1] */
+  const int64_t* obj_threshold_ns; /* [O] */
+  const int32_t* seg_cluster;      /* [S] */
+  const int64_t* seg_desired;      /* [S] */
+  const uint8_t* seg_flags;        /* [S] KAD_MIG_SEG_* */
+  const int64_t* seg_pod_off;      /* [S + 1] */
+  const int64_t* pod_t_ns;         /* [P] */
+  const uint8_t* pod_flags;        /* [P] KAD_MIG_POD_* */
+  const int32_t* old_off;          /* [O + 1] */
+  const int32_t* old_cluster;      /* [n_old] */
+  const int64_t* old_cap;          /* [n_old] */
+} kad_migrate_batch;
+typedef struct kad_migrate_view {
+  int32_t* uns;         /* [S] */
+  int64_t* next_cross;  /* [S] */
+  int64_t* cap;         /* [S] */
+  uint8_t* changed;     /* [O] */
+  int32_t* n_written;   /* [O] */
+  int64_t* retry_after; /* [O] */
+  uint8_t* backoff;     /* [O] */
+} kad_migrate_view;
+int kad_migrate_estimate(kad_ctx* ctx, const kad_migrate_batch* batch, const kad_migrate_view* out);
+/* Host only (no device, no ctx): the same validation against a snapshot of n_clusters clusters. */
+int kad_migrate_check(const kad_migrate_batch* batch, const kad_migrate_view* out, int32_t n_clusters);
+/* Device time of the last kad_migrate_estimate that launched, from HIP events: ms[0] = migrate_segment_kernel,
+ * ms[1] = migrate_object_kernel. No reference counterpart. */
+int kad_migrate_timing(kad_ctx* ctx, float ms[2]);
+/* What a kad_migrate_estimate launches, as the library's one decision computes it (csrc/kad_migrate.h
+ * route_migrate; no device work, no ctx) for n_segments segments holding n_pods pods, n_long of them longer
+ * than the route's long_min, in n_objects objects: out[KAD_MIG_ROUTE_FIELDS] is [0] the lanes per segment of
+ * the group path (a power of two in [8, 64] from the mean segment length), [1] long_min (a segment with MORE
+ * pods takes one 256-thread block), [2] block threads, [3] blocks of the group path, [4] blocks of the long
+ * path, [5] the distance between two consecutive segments of one lane group, [6] the lanes per object of the
+ * object kernel, [7] its blocks. kad_migrate_last_route: the same record for the last kad_migrate_estimate
+ * that launched (KAD_ESTATE before one). force_width / force_long_min of kad_migrate_debug_route (0: the
+ * route's own) replace [0] and [1] for the following calls on this ctx. Measurement / tests only. */
+#define KAD_MIG_ROUTE_FIELDS 8
+int kad_migrate_route_eval(int32_t n_segments, int64_t n_pods, int32_t n_long, int32_t n_objects, int32_t n_cu,
+                           int32_t* out);
+int kad_migrate_last_route(kad_ctx* ctx, int32_t* out);
+int kad_migrate_debug_route(kad_ctx* ctx, int32_t force_width, int32_t force_long_min);
+
 /* ------------------------------------------------ result application (§8 f3)
  * applySchedulingResult (pkg/controllers/scheduler/scheduler.go:632-695) writes a unit's result into its
  * federated object: the scheduler controller's placement (util.SetPlacementClusterNames,

@@ -384,6 +384,43 @@ class BatchReconciler:
         placer = FL.FollowerPlacer(self.ctx, snap)
         return placer.apply(followers, desired, fol_off, fol_leader, **args), errors
 
+    # ------------------------------------------------------------------ auto migration
+    def reconcile_auto_migration(self, objs: Sequence[dict], cluster_objs: Sequence[Sequence[Tuple[str, dict]]],
+                                 pods: Sequence[Sequence], now_ns: int,
+                                 clusters: Optional[List[T.FederatedCluster]] = None):
+        """The auto-migration controller's reconcile for a batch
+        (pkg/controllers/automigration/controller.go:178-290): ``cluster_objs[i]`` are object i's (cluster name,
+        member-cluster object) pairs, ``pods[i][j]`` the pod dicts of pair j or an exception object for a listing
+        that failed (automigration.PodListError). Objects without a parseable threshold annotation lose the
+        info annotation on the host (:217-224); the others are counted and compared in one
+        kad_migrate_estimate and only the changed ones get the annotation rewritten, in place.
+
+        The cluster ids are those of the resident snapshot (``clusters``: upload these first; None: the
+        snapshot the last reconcile left). Returns, per object, (result, estimatedCapacity, needsUpdate):
+        result is None (worker.StatusAllOK) or (retry_after_ns or None, backoff); estimatedCapacity is None
+        for a disabled object."""
+        from . import automigration as AM
+
+        snap = self.scheduler.set_clusters(clusters) if clusters is not None else self.ctx.snap
+        if snap is None:
+            raise ValueError("no snapshot is resident: pass clusters")
+        batch = AM.MigrationBatch(self.type_config, snap.names, now_ns)
+        out: list = [None] * len(objs)
+        members = []
+        for i, obj in enumerate(objs):
+            thr = AM.threshold_of(obj)
+            if thr is None:
+                out[i] = (None, None, AM.apply(obj, None, enabled=False))
+            else:
+                batch.add(obj, thr, cluster_objs[i], pods[i])
+                members.append(i)
+        if members:
+            r = self.ctx.migrate_estimate(**batch.arrays())
+            updated = batch.apply([objs[i] for i in members], r)
+            for k, i in enumerate(members):
+                out[i] = (batch.result(r, k), batch.capacities(r, k), updated[k])
+        return out
+
     # ------------------------------------------------------------------ the reconcile over JSON texts
     def reconcile_texts(self, texts: Sequence, policies: Sequence, clusters: List[T.FederatedCluster],
                         profiles: Optional[Dict[str, Optional[dict]]] = None

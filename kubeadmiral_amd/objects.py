@@ -191,6 +191,8 @@ class FederatedTypeConfig:
     plural_name: str = ""
     scope: str = "Namespaced"
     replicas_spec: str = ""      # Spec.PathDefinition.ReplicasSpec, dot path under the template
+    replicas_status: str = ""        # Spec.PathDefinition.ReplicasStatus (auto migration: total replicas)
+    ready_replicas_status: str = ""  # Spec.PathDefinition.ReadyReplicasStatus (auto migration: ready replicas)
 
     @property
     def namespaced(self) -> bool:

@@ -77,6 +77,21 @@ class FollowerView(ctypes.Structure):  # kad_follower_view
                 ("out_cluster", ctypes.c_void_p)]
 
 
+class MigrateBatch(ctypes.Structure):  # kad_migrate_batch
+    _fields_ = [("n_ids", ctypes.c_int32), ("n_objects", ctypes.c_int32), ("n_segments", ctypes.c_int32),
+                ("n_old", ctypes.c_int32), ("n_pods", ctypes.c_int64), ("now_ns", ctypes.c_int64),
+                ("obj_seg_off", ctypes.c_void_p), ("obj_threshold_ns", ctypes.c_void_p), ("seg_cluster", ctypes.c_void_p),
+                ("seg_desired", ctypes.c_void_p), ("seg_flags", ctypes.c_void_p), ("seg_pod_off", ctypes.c_void_p),
+                ("pod_t_ns", ctypes.c_void_p), ("pod_flags", ctypes.c_void_p), ("old_off", ctypes.c_void_p),
+                ("old_cluster", ctypes.c_void_p), ("old_cap", ctypes.c_void_p)]
+
+
+class MigrateView(ctypes.Structure):  # kad_migrate_view
+    _fields_ = [("uns", ctypes.c_void_p), ("next_cross", ctypes.c_void_p), ("cap", ctypes.c_void_p),
+                ("changed", ctypes.c_void_p), ("n_written", ctypes.c_void_p), ("retry_after", ctypes.c_void_p),
+                ("backoff", ctypes.c_void_p)]
+
+
 _lib = None
 
 
@@ -178,6 +193,14 @@ def load_library(path: str = LIB_PATH):
         L.kad_follower_timing.argtypes = [P, P]
         L.kad_follower_route_eval.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, P]
         L.kad_follower_last_route.argtypes = [P, P]
+    if hasattr(L, "kad_migrate_estimate"):
+        L.kad_migrate_estimate.argtypes = [P, P, P]
+        L.kad_migrate_check.argtypes = [P, P, ctypes.c_int32]
+        L.kad_migrate_timing.argtypes = [P, P]
+        L.kad_migrate_route_eval.argtypes = [ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                             ctypes.c_int32, P]
+        L.kad_migrate_last_route.argtypes = [P, P]
+        L.kad_migrate_debug_route.argtypes = [P, ctypes.c_int32, ctypes.c_int32]
     L.kad_debug_inject_fault.argtypes = [P, I]
     L.kad_debug_plan_force_workspace.argtypes = [P, I]
     L.kad_trigger_suffix_upload.argtypes = [P, P, SZ]
@@ -303,6 +326,46 @@ def follower_check(n_clusters: int, n_units: int, n_ids: int, followers, **kw) -
     of ``n_clusters`` clusters and a scheduled batch of ``n_units`` units (-1: none); no GPU. Returns the code."""
     b, v, _keepalive, _ = follower_args(n_ids, followers, **kw)
     return load_library().kad_follower_check(ctypes.byref(b), ctypes.byref(v), n_clusters, n_units)
+
+
+MIGRATE_ROUTE = ("width", "long_min", "threads", "grid", "long_grid", "stride", "obj_width", "obj_grid")
+
+
+def migrate_route_eval(n_segments: int, n_pods: int, n_long: int, n_objects: int, n_cu: int = 256) -> dict:
+    """kad_migrate_route_eval: the launch decision of a migrate_estimate (needs no GPU)."""
+    out = (ctypes.c_int32 * len(MIGRATE_ROUTE))()
+    rc = load_library().kad_migrate_route_eval(n_segments, n_pods, n_long, n_objects, n_cu, out)
+    if rc != 0:
+        raise ValueError(f"kad_migrate_route_eval: {rc}")
+    return dict(zip(MIGRATE_ROUTE, out))
+
+
+_MIGRATE_IN = (("obj_seg_off", np.int32), ("obj_threshold_ns", np.int64), ("seg_cluster", np.int32),
+               ("seg_desired", np.int64), ("seg_flags", np.uint8), ("seg_pod_off", np.int64), ("pod_t_ns", np.int64),
+               ("pod_flags", np.uint8), ("old_off", np.int32), ("old_cluster", np.int32), ("old_cap", np.int64))
+_MIGRATE_OUT = (("uns", np.int32, "S"), ("next_cross", np.int64, "S"), ("cap", np.int64, "S"), ("changed", np.uint8, "O"),
+                ("n_written", np.int32, "O"), ("retry_after", np.int64, "O"), ("backoff", np.uint8, "O"))
+
+
+def migrate_args(n_ids: int, now_ns: int, **arrays):
+    """The kad_migrate_batch / kad_migrate_view of one call with the arrays that back them (the batch's
+    fields by name; the counts are taken from the arrays as they are, so that a malformed batch reaches the
+    library's validation). Returns (batch, view, the input arrays, the output arrays by name)."""
+    a = {k: np.ascontiguousarray(arrays[k], dt).reshape(-1) for k, dt in _MIGRATE_IN}
+    O_, S_ = len(a["obj_threshold_ns"]), len(a["seg_cluster"])
+    n = {"O": O_, "S": S_}
+    out = {k: np.zeros(max(1, n[dim]), dt) for k, dt, dim in _MIGRATE_OUT}
+    b = MigrateBatch(int(n_ids), O_, S_, len(a["old_cluster"]), len(a["pod_t_ns"]), int(now_ns),
+                     *(a[k].ctypes.data if len(a[k]) else None for k, _ in _MIGRATE_IN))
+    v = MigrateView(*(out[k].ctypes.data for k, _, _ in _MIGRATE_OUT))
+    return b, v, a, {k: out[k][:n[dim]] for k, _, dim in _MIGRATE_OUT}
+
+
+def migrate_check(n_clusters: int, n_ids: int, now_ns: int, **arrays) -> int:
+    """kad_migrate_check: kad_migrate_estimate's validation of :func:`migrate_args` arguments against a
+    snapshot of ``n_clusters`` clusters; no GPU. Returns the code."""
+    b, v, _keepalive, _ = migrate_args(n_ids, now_ns, **arrays)
+    return load_library().kad_migrate_check(ctypes.byref(b), ctypes.byref(v), n_clusters)
 
 
 class Context:
@@ -580,6 +643,31 @@ class Context:
         out = (ctypes.c_int32 * len(FOLLOWER_ROUTE))()
         self._chk(self.L.kad_follower_last_route(self.h, out))
         return _follower_route_dict(out)
+
+    def migrate_estimate(self, n_ids: int, now_ns: int, **arrays) -> dict:
+        """kad_migrate_estimate → {uns[S], next_cross[S], cap[S], changed[O], n_written[O], retry_after[O],
+        backoff[O]}. Arguments as :func:`migrate_args` (automigration.MigrationBatch.arrays())."""
+        b, v, _keepalive, out = migrate_args(n_ids, now_ns, **arrays)
+        self._chk(self.L.kad_migrate_estimate(self.h, ctypes.byref(b), ctypes.byref(v)))
+        return out
+
+    def migrate_timing(self):
+        """kad_migrate_timing: device ms of the last migrate_estimate() — (migrate_segment_kernel,
+        migrate_object_kernel)."""
+        ms = (ctypes.c_float * 2)()
+        self._chk(self.L.kad_migrate_timing(self.h, ms))
+        return float(ms[0]), float(ms[1])
+
+    def migrate_last_route(self) -> dict:
+        """kad_migrate_last_route: what the last migrate_estimate() launched (migrate_route_eval's record)."""
+        out = (ctypes.c_int32 * len(MIGRATE_ROUTE))()
+        self._chk(self.L.kad_migrate_last_route(self.h, out))
+        return dict(zip(MIGRATE_ROUTE, out))
+
+    def migrate_debug_route(self, width: int = 0, long_min: int = 0) -> None:
+        """kad_migrate_debug_route: the group width / long_min of the following migrate_estimate() calls
+        (0: the route's own). Measurement only."""
+        self._chk(self.L.kad_migrate_debug_route(self.h, width, long_min))
 
     def select_rows(self, rows: Sequence[Sequence[int]], max_clusters: Sequence[Optional[int]], flags: int = 0):
         """MaxCluster on explicit score rows → per row (status, sorted selected positions)."""

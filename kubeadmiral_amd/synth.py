@@ -1083,3 +1083,136 @@ def gen_followers(seed: int, lead_off, lead_cluster, n_ids: int, per_leader: flo
         cur_off[i + 1] = cur_off[i] + len(u)
     cur_cluster = np.concatenate(cur).astype(np.int32) if cur else np.zeros(0, np.int32)
     return (fol_off, fol_leader, cur_off, cur_cluster, has), stale
+
+
+# ------------------------------------------------------------ auto migration (kad_migrate_estimate)
+MIGRATION_NOW_NS = 1_760_000_000 * 10**9  # a fixed "now" (October 2025) for seeded workloads
+
+
+def gen_migration(seed: int, W: int, C: int, ready_share: float = 0.9, max_segments: int = 5, replicas=(1, 100),
+                  unschedulable: float = 0.3, changed: float = 0.05, extra_ids: int = 0, now_ns: int = MIGRATION_NOW_NS,
+                  thresholds_s=(30, 60, 300)):
+    """A synthetic auto-migration batch as kad_migrate_estimate's arrays: ``W`` objects with a threshold out
+    of ``thresholds_s`` (seconds), each on 1..``max_segments`` member clusters out of ``C + extra_ids`` ids. A share
+    ``ready_share`` of the segments has total == ready (KAD_MIG_SEG_SKIP, no pods; 1 % of them a failed listing
+    with backoff); the others hold about as many pods as desired replicas (``replicas``, the range of the
+    synthetic Deployments), a share ``unschedulable`` of them unschedulable since a time within two minutes
+    around the threshold, 5 % deleting, 1 % of the unschedulable ones without a transition time. The existing
+    annotation is the batch's own result except for a share ``changed`` of the objects, which lack its first
+    entry or, where it is empty, hold one stale entry. Returns (arrays — the keyword arguments of
+    Context.migrate_estimate —, the changed mask)."""
+    from . import automigration as AM
+
+    rng = np.random.default_rng([seed, 0xA070])
+    n_ids = C + extra_ids
+    max_segments = max(1, min(max_segments, n_ids))
+    nseg = rng.integers(1, max_segments + 1, W)
+    so = np.zeros(W + 1, np.int64)
+    so[1:] = np.cumsum(nseg)
+    S = int(so[-1])
+    owner = np.repeat(np.arange(W), nseg)
+    k = np.arange(S) - so[owner]
+    step = rng.integers(1, max(1, n_ids // max_segments) + 1, W)
+    start = (rng.random(W) * (n_ids - step * (nseg - 1))).astype(np.int64)
+    seg_cluster = (start[owner] + k * step[owner]).astype(np.int32)
+    desired = rng.integers(replicas[0], replicas[1] + 1, S)
+    skip = rng.random(S) < ready_share
+    flags = np.where(skip, AM.SEG_SKIP, 0).astype(np.uint8)
+    flags[skip & (rng.random(S) < 0.01)] |= AM.SEG_BACKOFF
+    npods = np.where(skip, 0, np.maximum(0, desired + rng.integers(-2, 3, S)))
+    po = np.zeros(S + 1, np.int64)
+    po[1:] = np.cumsum(npods)
+    P = int(po[-1])
+    thr = rng.choice(np.array(thresholds_s, np.int64) * 10**9, W)
+    pod_obj = owner[np.repeat(np.arange(S), npods)]
+    pf = np.where(rng.random(P) < unschedulable, AM.POD_UNSCHED, 0).astype(np.uint8)
+    pf[rng.random(P) < 0.05] |= AM.POD_DELETING
+    pf[(rng.random(P) < 0.01) & ((pf & AM.POD_UNSCHED) != 0)] |= AM.POD_TZERO
+    pt = now_ns - thr[pod_obj] + rng.integers(-60 * 10**9, 60 * 10**9 + 1, P)
+    pt[(pf & AM.POD_TZERO) != 0] = 0
+    a = dict(n_ids=n_ids, now_ns=int(now_ns), obj_seg_off=so.astype(np.int32), obj_threshold_ns=thr,
+             seg_cluster=seg_cluster, seg_desired=desired.astype(np.int64), seg_flags=flags, seg_pod_off=po,
+             pod_t_ns=pt.astype(np.int64), pod_flags=pf, old_off=np.zeros(W + 1, np.int32),
+             old_cluster=np.zeros(0, np.int32), old_cap=np.zeros(0, np.int64))
+    r = AM.migrate_numpy(**a)
+    written = r["cap"] >= 0
+    stale = rng.random(W) < changed
+    first = np.zeros(S, bool)
+    wi = np.nonzero(written)[0]
+    if len(wi):
+        first[wi[np.r_[True, owner[wi][1:] != owner[wi][:-1]]]] = True
+    keep = written & ~(first & stale[owner])
+    n_old = np.bincount(owner[keep], minlength=W)
+    fake = stale & (r["n_written"] == 0)  # nothing to drop: one stale entry instead
+    oc, ov, oo = seg_cluster[keep], r["cap"][keep], owner[keep]
+    if fake.any():
+        fo = np.nonzero(fake)[0]
+        oc = np.concatenate([oc, seg_cluster[so[fo]]])
+        ov = np.concatenate([ov, np.full(len(fo), 7, np.int64)])
+        oo = np.concatenate([oo, fo])
+        order = np.argsort(oo, kind="stable")
+        oc, ov = oc[order], ov[order]
+        n_old = n_old + fake
+    a["old_off"] = np.r_[0, np.cumsum(n_old)].astype(np.int32)
+    a["old_cluster"], a["old_cap"] = oc.astype(np.int32), ov.astype(np.int64)
+    return a, stale
+
+
+def migration_objects(a: dict, names, type_config=None):
+    """The batch of :func:`gen_migration` as the controller sees it: federated objects with the threshold and
+    the existing annotation, per object the (cluster name, member Deployment) pairs, and per pair the pod dicts
+    (a PodListError for a backoff segment). ``names``: cluster names by id (``a['n_ids']`` of them). For small
+    batches: tests. Returns (type_config, objs, cluster_objs, pods)."""
+    import datetime
+
+    from . import automigration as AM
+    from . import objects as O
+
+    ftc = type_config or O.FederatedTypeConfig("apps", "v1", "Deployment", "deployments", "Namespaced", "spec.replicas",
+                                               "status.replicas", "status.readyReplicas")
+    epoch = datetime.datetime(1970, 1, 1)
+
+    def rfc3339(ns: int) -> str:
+        t = epoch + datetime.timedelta(microseconds=ns // 1000)
+        return t.strftime("%Y-%m-%dT%H:%M:%S") + f".{ns % 10**9:09d}Z"
+
+    objs, cobjs, pods = [], [], []
+    for i in range(len(a["obj_threshold_ns"])):
+        ann = {O.POD_UNSCHEDULABLE_THRESHOLD_ANNOTATION: O.duration_string(int(a["obj_threshold_ns"][i]))}
+        q0, q1 = int(a["old_off"][i]), int(a["old_off"][i + 1])
+        if q1 > q0:
+            ann[O.AUTO_MIGRATION_INFO_ANNOTATION] = AM.marshal_info(
+                {names[int(a["old_cluster"][q])]: int(a["old_cap"][q]) for q in range(q0, q1)})
+        objs.append({"apiVersion": "types.kubeadmiral.io/v1alpha1", "kind": "FederatedDeployment",
+                     "metadata": {"name": f"app-{i}", "namespace": "default", "annotations": ann},
+                     "spec": {"template": {"apiVersion": "apps/v1", "kind": "Deployment",
+                                           "metadata": {"name": f"app-{i}", "namespace": "default"},
+                                           "spec": {"replicas": 1}}}})
+        co, pl = [], []
+        for s in range(int(a["obj_seg_off"][i]), int(a["obj_seg_off"][i + 1])):
+            sf, desired = int(a["seg_flags"][s]), int(a["seg_desired"][s])
+            p0, p1 = int(a["seg_pod_off"][s]), int(a["seg_pod_off"][s + 1])
+            skip = bool(sf & AM.SEG_SKIP) and not sf & AM.SEG_BACKOFF
+            status = {"replicas": desired, "readyReplicas": desired if skip else max(0, desired - 1)}
+            co.append((names[int(a["seg_cluster"][s])],
+                       {"apiVersion": "apps/v1", "kind": "Deployment", "spec": {"replicas": desired}, "status": status}))
+            if sf & AM.SEG_BACKOFF:
+                pl.append(AM.PodListError("listing failed", needs_backoff=True))
+                continue
+            seg = []
+            for p in range(p0, p1):
+                f = int(a["pod_flags"][p])
+                cond = {"type": "PodScheduled", "status": "True"}
+                if f & AM.POD_UNSCHED:
+                    cond = {"type": "PodScheduled", "status": "False", "reason": "Unschedulable"}
+                if not f & AM.POD_TZERO:
+                    cond["lastTransitionTime"] = rfc3339(int(a["pod_t_ns"][p]))
+                pod = {"metadata": {"name": f"app-{i}-{p}"}, "status": {"conditions": [cond]}}
+                if f & AM.POD_DELETING:
+                    pod["metadata"]["deletionTimestamp"] = rfc3339(int(a["now_ns"]))
+                seg.append(pod)
+            pl.append(seg)
+        objs[-1]["spec"]["template"]["spec"]["replicas"] = int(a["seg_desired"][int(a["obj_seg_off"][i])])
+        cobjs.append(co)
+        pods.append(pl)
+    return ftc, objs, cobjs, pods
