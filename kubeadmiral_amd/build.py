@@ -17,7 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libkad.so")
 SOURCES = ["kad_kernels.hip", "kad_trigger.hip", "kad_delta.hip", "kad_diff.hip", "kad_explain.hip", "kad_override.hip", "kad_follower.hip", "kad_migrate.hip", "kad_api.hip", "kad_pack.cpp", "kad_objects.cpp"]
-HEADERS = ["kad_device.h", "kad_layout.h", "kad_route.h", "kad_wave.h", "kad_affinity.h", "kad_select.h", "kad_plan.h", "kad_pool.h", "kad_follower.h", "kad_migrate.h"]
+HEADERS = ["kad_device.h", "kad_layout.h", "kad_route.h", "kad_wave.h", "kad_affinity.h", "kad_select.h", "kad_plan.h", "kad_pool.h", "kad_follower.h", "kad_migrate.h", "kad_ctx.h", "kad_arena.h"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("KAD_OFFLOAD_ARCH", "gfx950")
 

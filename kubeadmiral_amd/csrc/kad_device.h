@@ -202,8 +202,6 @@ struct TriggerDev {
 };
 int64_t trigger_segment_len(int64_t suffix_len);
 int64_t trigger_table_count(int64_t suffix_len);
-hipError_t launch_trigger_summary(const TriggerDev& t, hipStream_t st);
-hipError_t launch_trigger_objects(const TriggerDev& t, hipStream_t st);
 
 // bytes of per-wave scratch for the filter/score/select kernel at C clusters
 size_t select_wave_bytes(int C);
@@ -305,7 +303,6 @@ struct ExplainArgs {
   int32_t* fit_detail;  // [n_units][3] or null
   uint8_t* first_fail;  // [n_units][C] or null
 };
-hipError_t launch_explain(const ExplainArgs& a, hipStream_t st);
 
 // kad_override_match (kad_override.hip): the resident policy set, its rows and one batch of objects.
 struct OverrideDev {
@@ -333,8 +330,6 @@ struct OverrideDev {
   int32_t* status;               // [n_obj]
   uint32_t* matched;             // [n_slots][RW]
 };
-hipError_t launch_override_rule_rows(const OverrideDev& o, hipStream_t st);
-hipError_t launch_override_match(const OverrideDev& o, hipStream_t st);
 
 // kad_snapshot_update: scatter the changed clusters' columns of every snapshot
 // array from a resident delta blob into the resident snapshot blob.
@@ -367,6 +362,5 @@ struct ResultDiffDev {
   const uint8_t* ov_kind;
   uint32_t* out;           // [W] KAD_DIFF_*
 };
-hipError_t launch_result_diff(const ResultDiffDev& d, hipStream_t st);
 
 }  // namespace kad

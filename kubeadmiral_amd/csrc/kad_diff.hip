@@ -74,3 +74,85 @@ hipError_t launch_result_diff(const ResultDiffDev& d, hipStream_t st) {
 }
 
 }  // namespace kad
+
+// ------------------------------------------------------ host half: kad_result_diff
+#include "kad_arena.h"
+
+using namespace kad;
+
+extern "C" {
+
+int kad_result_diff(kad_ctx* c, const kad_result_state* st, uint32_t* out) {
+  return entry(c, st && out, [&]() -> int {
+    if (!c->ran || !c->have_batch) return fail(c, KAD_ESTATE, "no scheduled batch resident");
+    // this ctx's units (a kad_group member: its shard, whose out_off keeps the batch-wide slot numbers that
+    // out_dev's shifted slot arrays are indexed by)
+    const int W = (int)c->unit_n, C = c->sd.C;
+    if (st->n_units != W) return fail(c, KAD_EINVAL, "state n_units differs from the resident batch");
+    if (W == 0) return KAD_OK;
+    if (!st->place_off || !st->place_has || !st->ovr_off) return fail(c, KAD_EINVAL, "null state array");
+    if (off_bad(st->place_off, W) || off_bad(st->ovr_off, W)) return fail(c, KAD_EINVAL, "state offsets not monotone from 0");
+    const int64_t NP = st->place_off[W], NO = st->ovr_off[W];
+    if ((NP && !st->place_cluster) || (NO && (!st->ovr_cluster || !st->ovr_value || !st->ovr_kind)))
+      return fail(c, KAD_EINVAL, "null state array");
+    if (csr_bad(st->place_off, st->place_cluster, W, -1, C)) return fail(c, KAD_EINVAL, "placement cluster out of range");
+    if (csr_bad(st->ovr_off, st->ovr_cluster, W, -1, C)) return fail(c, KAD_EINVAL, "override cluster out of range");
+    // canonical placements: sorted unique snapshot positions; names outside the snapshot → uflag bit 1
+    std::vector<int32_t> cnt((size_t)W + 1, 0);
+    std::vector<uint8_t> uflag((size_t)W);
+    std::vector<int32_t> ids((size_t)NP);
+    host_parallel(W, [&](int lo, int hi) {
+      for (int w = lo; w < hi; w++) {
+        int32_t* b = ids.data() + st->place_off[w];
+        const int m = st->place_off[w + 1] - st->place_off[w];
+        std::copy(st->place_cluster + st->place_off[w], st->place_cluster + st->place_off[w + 1], b);
+        std::sort(b, b + m);
+        const int u = (int)(std::unique(b, b + m) - b);
+        const bool unknown = u > 0 && b[0] < 0;
+        cnt[(size_t)w + 1] = unknown ? u - 1 : u;
+        if (unknown) std::copy(b + 1, b + u, b);  // drop the -1
+        uflag[w] = (uint8_t)((st->place_has[w] ? 1 : 0) | (unknown ? 2 : 0));
+      }
+    });
+    std::vector<int32_t> pl_off((size_t)W + 1, 0);
+    for (int w = 0; w < W; w++) pl_off[(size_t)w + 1] = pl_off[w] + cnt[(size_t)w + 1];
+    std::vector<int32_t> pl_id((size_t)pl_off[W] + 1);
+    host_parallel(W, [&](int lo, int hi) {
+      for (int w = lo; w < hi; w++)
+        std::copy(ids.data() + st->place_off[w], ids.data() + st->place_off[w] + cnt[(size_t)w + 1], pl_id.data() + pl_off[w]);
+    });
+    // one device buffer: [pl_off | pl_id | ov_off | ov_id | ov_val | uflag | ov_kind | out]; the kernel may read
+    // one element past pl_id, ov_id, ov_val and ov_kind
+    const size_t w = (size_t)W, no = (size_t)NO;
+    Arena a;
+    const Part p_ploff = a.in(pl_off.data(), 4 * (w + 1)), p_plid = a.in(pl_id.data(), 4 * (size_t)pl_off[W], 4),
+               p_ovoff = a.in(st->ovr_off, 4 * (w + 1)), p_ovid = a.in(st->ovr_cluster, 4 * no, 4),
+               p_ovval = a.in(st->ovr_value, 8 * no, 8), p_uf = a.in(uflag.data(), w), p_ovk = a.in(st->ovr_kind, no, 1),
+               o_out = a.out(4 * w);
+    HIPCHK(c, hipSetDevice(c->device));
+    DevBuf& buf = c->stage[STG_DIFF].buf;
+    if (int r = a.commit(c, buf)) return r;
+    ResultDiffDev dd{};
+    dd.W = W;
+    dd.status = c->d_status;
+    dd.count = c->d_count;
+    const OutDev od = out_dev(c);
+    dd.cluster = od.cluster;
+    dd.replicas = od.replicas;
+    dd.out_off = c->bd.out_off;
+    dd.pl_off = a.ptr<const int32_t>(buf, p_ploff);
+    dd.pl_id = a.ptr<const int32_t>(buf, p_plid);
+    dd.uflag = a.ptr<const uint8_t>(buf, p_uf);
+    dd.ov_off = a.ptr<const int32_t>(buf, p_ovoff);
+    dd.ov_id = a.ptr<const int32_t>(buf, p_ovid);
+    dd.ov_val = a.ptr<const int64_t>(buf, p_ovval);
+    dd.ov_kind = a.ptr<const uint8_t>(buf, p_ovk);
+    dd.out = a.ptr<uint32_t>(buf, o_out);
+    HIPCHK(c, launch_result_diff(dd, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out, dd.out, 4 * w, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));  // the caller's state arrays are free on return
+    return KAD_OK;
+  });
+}
+
+}  // extern "C"

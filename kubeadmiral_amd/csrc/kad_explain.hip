@@ -182,3 +182,79 @@ hipError_t launch_explain(const ExplainArgs& a, hipStream_t st) {
 }
 
 }  // namespace kad
+
+// ------------------------------------------------------ host half: kad_explain
+#include "kad_arena.h"
+
+using namespace kad;
+
+extern "C" {
+
+// The filter diagnosis of the listed units (kad_explain.hip). Reads the resident snapshot and batch and the
+// requirement rows (rebuilt here by the launch schedule_locked uses: ~10 us at the bench sizes, and no
+// currency flag to keep through every upload and update path); writes only its own buffer.
+int kad_explain(kad_ctx* c, const kad_profile* p, const int32_t* order, int n_order, const int32_t* unit_idx,
+                int n_units, const kad_explain_view* out) {
+  return entry(c, true, [&]() -> int {
+    if (!c->have_snapshot || !c->have_batch) return fail(c, KAD_ESTATE, "snapshot and batch must be uploaded first");
+    if (int r = validate_profile(c, p)) return r;
+    if (p->filter_mask != c->batch_hdr.packed_filter_mask)
+      return fail(c, KAD_EINVAL, "profile differs from the one the batch was packed for");
+    if (n_order < 0 || n_order > 5 || (n_order && !order)) return fail(c, KAD_EINVAL, "filter order: 0..5 plugin ids");
+    uint32_t seen = 0, packed = 0;
+    for (int k = 0; k < n_order; k++) {
+      if (order[k] < 0 || order[k] > KAD_PL_CLUSTER_AFFINITY || (seen >> order[k] & 1))
+        return fail(c, KAD_EINVAL, "filter order: not a filter plugin id, or listed twice");
+      seen |= 1u << order[k];
+      packed |= (uint32_t)order[k] << (4 * k);
+    }
+    if (seen != p->filter_mask) return fail(c, KAD_EINVAL, "filter order is not a permutation of the profile's filter mask");
+    if (n_units < 0 || (n_units && (!unit_idx || !out || !out->rejected || !out->feasible)))
+      return fail(c, KAD_EINVAL, "unit list or output view missing");
+    const int W = c->bd.W;
+    for (int i = 0; i < n_units; i++)
+      if (unit_idx[i] < 0 || unit_idx[i] >= W)
+        return fail(c, KAD_EINVAL, "unit_idx[" + std::to_string(i) + "] = " + std::to_string(unit_idx[i]) +
+                                       " outside the batch's " + std::to_string(W) + " units");
+    if (n_units == 0) return KAD_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t n = (size_t)n_units, C = (size_t)c->sd.C;
+    Arena ar;
+    const Part p_units = ar.in(unit_idx, 4 * n), o_rej = ar.out(20 * n), o_feas = ar.out(4 * n),
+               o_fit = out->fit_detail ? ar.out(12 * n) : Arena::absent(),
+               o_ff = out->first_fail ? ar.out(n * C) : Arena::absent();
+    Stage& stg = c->stage[STG_EXPLAIN];
+    if (int r = ar.commit(c, stg.buf)) return r;
+    ExplainArgs a{};
+    a.s = c->sd;
+    a.b = c->bd;
+    a.filter_mask = p->filter_mask;
+    a.order = packed;
+    a.n_order = n_order;
+    a.units = ar.ptr<const int32_t>(stg.buf, p_units);
+    a.n_units = n_units;
+    a.rejected = ar.ptr<int32_t>(stg.buf, o_rej);
+    a.feasible = ar.ptr<int32_t>(stg.buf, o_feas);
+    a.fit_detail = ar.ptr<int32_t>(stg.buf, o_fit);
+    a.first_fail = ar.ptr<uint8_t>(stg.buf, o_ff);
+    HIPCHK(c, hipEventRecord(stg.ev[0], c->stream));
+    bool zeroed = false;
+    HIPCHK(c, launch_req_masks(c->sd, c->bd, c->stream, false, &zeroed));
+    HIPCHK(c, hipEventRecord(stg.ev[1], c->stream));
+    HIPCHK(c, launch_explain(a, c->stream));
+    HIPCHK(c, hipEventRecord(stg.ev[2], c->stream));
+    stg.ran = true;
+    HIPCHK(c, hipMemcpyAsync(out->rejected, a.rejected, 20 * n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out->feasible, a.feasible, 4 * n, hipMemcpyDeviceToHost, c->stream));
+    if (a.fit_detail) HIPCHK(c, hipMemcpyAsync(out->fit_detail, a.fit_detail, 12 * n, hipMemcpyDeviceToHost, c->stream));
+    if (a.first_fail && C) HIPCHK(c, hipMemcpyAsync(out->first_fail, a.first_fail, n * C, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return KAD_OK;
+  });
+}
+
+int kad_explain_timing(kad_ctx* c, float ms[2]) {
+  return entry(c, ms != nullptr, [&] { return stage_timing(c, c->stage[STG_EXPLAIN], 2, ms, "no kad_explain ran"); });
+}
+
+}  // extern "C"

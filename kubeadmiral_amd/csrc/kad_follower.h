@@ -73,10 +73,4 @@ inline FollowerRoute route_follower(int n_ids, int F, int n_cu) {
   return r;
 }
 
-// union + compare (changed, count), then the scan of the emitted counts into fout_off
-hipError_t launch_follower_union(const FollowerDev& d, const FollowerRoute& r, hipStream_t st);
-hipError_t launch_follower_scan(const FollowerDev& d, hipStream_t st);
-// writes out_cluster unless fout_off[F] > capacity (checked on the device: no host round trip in between)
-hipError_t launch_follower_emit(const FollowerDev& d, const FollowerRoute& r, hipStream_t st);
-
 }  // namespace kad

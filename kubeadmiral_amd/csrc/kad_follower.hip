@@ -327,3 +327,174 @@ hipError_t launch_follower_emit(const FollowerDev& d, const FollowerRoute& r, hi
 }
 
 }  // namespace kad
+
+// ------------------------------------------------------ host half: kad_follower_*
+#include "kad_arena.h"
+
+using namespace kad;
+
+extern "C" {
+
+// ------------------------------------------------------ follower scheduling
+// Every offset array monotone from 0, every id in [0, n_ids), every leader index in [-1, n_leaders): all of
+// it on the host, before anything is copied or launched. C = the snapshot's clusters; W = the resident
+// units a resident-mode batch reads (ignored in explicit mode).
+static int validate_follower(const kad_follower_batch* b, const kad_follower_view* out, int C, int64_t W,
+                             std::string* err) {
+  auto bad = [&](const char* m) {
+    *err = m;
+    return KAD_EINVAL;
+  };
+  const int64_t n_ids = b->n_ids, L = b->n_leaders, F = b->n_followers;
+  if (n_ids < C || n_ids > FOL_MAX_IDS) return bad("n_ids must lie in [the snapshot's clusters, 131072]");
+  if (L < 0 || F < 0 || b->out_capacity < 0) return bad("negative count or capacity");
+  if (b->flags & ~(uint32_t)KAD_FOL_EMIT_ALL) return bad("unknown flag");
+  const bool resident = b->lead_off == nullptr;
+  if (!resident) {
+    if (csr_bad(b->lead_off, b->lead_cluster, L, 0, n_ids)) return bad("lead_off / lead_cluster malformed or id out of range");
+  } else {
+    if (L < W) return bad("resident mode: n_leaders is less than the resident batch's units");
+    if (b->sched_off && csr_bad(b->sched_off, b->sched_cluster, W, 0, n_ids))
+      return bad("sched_off / sched_cluster malformed or id out of range");
+  }
+  if (b->keep_off && csr_bad(b->keep_off, b->keep_cluster, L, 0, n_ids))
+    return bad("keep_off / keep_cluster malformed or id out of range");
+  if (csr_bad(b->fol_off, b->fol_leader, F, -1, L)) return bad("fol_off / fol_leader malformed or leader index out of range");
+  if (csr_bad(b->cur_off, b->cur_cluster, F, 0, n_ids)) return bad("cur_off / cur_cluster malformed or id out of range");
+  if (F && !b->cur_has) return bad("cur_has missing");
+  {
+    const int32_t* co = b->cur_off;
+    const uint8_t* ch = b->cur_has;
+    if (first_bad(F, [&](int64_t i) { return !ch[i] && co[i + 1] > co[i]; }) >= 0)
+      return bad("cur_has = 0 with a non-empty cur range: a placement entry that does not exist holds no clusters");
+  }
+  if (!out || !out->out_off || (F && (!out->changed || !out->count)) || (b->out_capacity && !out->out_cluster))
+    return bad("output view missing");
+  return KAD_OK;
+}
+
+static int follower_union_locked(kad_ctx* c, const kad_follower_batch* b, const kad_follower_view* out) {
+  if (!c->have_snapshot) return fail(c, KAD_ESTATE, "a snapshot must be uploaded first");
+  const bool resident = b->lead_off == nullptr;
+  if (resident && c->group_member)
+    return fail(c, KAD_EUNSUPPORTED, "resident mode on a kad_group member: a follower's leaders may live in other shards");
+  if (resident && (!c->have_batch || !c->ran)) return fail(c, KAD_ESTATE, "nothing has been scheduled");
+  const int64_t W = resident ? c->unit_n : 0;
+  std::string err;
+  if (int r = validate_follower(b, out, c->sd.C, W, &err)) return fail(c, r, err);
+  const int F = b->n_followers, L = b->n_leaders;
+  out->out_off[0] = 0;
+  if (F == 0) return KAD_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const FollowerRoute route = route_follower(b->n_ids, F, n_cus());
+  // one buffer: the inputs, then changed / count / out_off / the scan's block sums / out_cluster
+  const size_t f = (size_t)F, l = (size_t)L, n_lead = resident ? 0 : (size_t)b->lead_off[L],
+               n_sched = resident && b->sched_off ? (size_t)b->sched_off[W] : 0, n_keep = b->keep_off ? (size_t)b->keep_off[L] : 0;
+  Arena a;
+  const Part p_lo = resident ? Arena::absent() : a.in(b->lead_off, 4 * (l + 1)), p_lc = a.in(b->lead_cluster, 4 * n_lead),
+             p_so = resident && b->sched_off ? a.in(b->sched_off, 4 * ((size_t)W + 1)) : Arena::absent(),
+             p_sc = a.in(b->sched_cluster, 4 * n_sched),
+             p_ko = b->keep_off ? a.in(b->keep_off, 4 * (l + 1)) : Arena::absent(), p_kc = a.in(b->keep_cluster, 4 * n_keep),
+             p_fo = a.in(b->fol_off, 4 * (f + 1)), p_fl = a.in(b->fol_leader, 4 * (size_t)b->fol_off[F]),
+             p_co = a.in(b->cur_off, 4 * (f + 1)), p_cc = a.in(b->cur_cluster, 4 * (size_t)b->cur_off[F]),
+             p_ch = a.in(b->cur_has, f);
+  const size_t scan_blocks = (f + 256 * FOL_SCAN_ITEMS - 1) / (256 * FOL_SCAN_ITEMS);
+  const Part o_changed = a.out(f), o_count = a.out(4 * f), o_off = a.out(8 * (f + 1)), o_sums = a.out(8 * scan_blocks),
+             o_cluster = a.out(4 * (size_t)b->out_capacity);
+  Stage& stg = c->stage[STG_FOLLOWER];
+  if (int r = a.commit(c, stg.buf)) return r;
+  FollowerDev fd{};
+  fd.n_ids = b->n_ids;
+  fd.nw = route.words;
+  fd.F = F;
+  fd.n_leaders = L;
+  fd.lead_off = a.ptr<const int32_t>(stg.buf, p_lo);
+  fd.lead_cluster = a.ptr<const int32_t>(stg.buf, p_lc);
+  fd.resident = resident ? 1 : 0;
+  fd.W = (int)W;
+  if (resident) {
+    fd.out_off = c->bd.out_off;
+    fd.cur_off = c->bd.cur_off;
+    fd.cur_id = c->bd.cur_id;
+    fd.res_status = c->d_status;
+    fd.res_count = c->d_count;
+    fd.res_cluster = c->d_cluster;
+    fd.slot_lo = c->slot_lo;
+  }
+  fd.sched_off = a.ptr<const int32_t>(stg.buf, p_so);
+  fd.sched_cluster = a.ptr<const int32_t>(stg.buf, p_sc);
+  fd.keep_off = a.ptr<const int32_t>(stg.buf, p_ko);
+  fd.keep_cluster = a.ptr<const int32_t>(stg.buf, p_kc);
+  fd.fol_off = a.ptr<const int32_t>(stg.buf, p_fo);
+  fd.fol_leader = a.ptr<const int32_t>(stg.buf, p_fl);
+  fd.fcur_off = a.ptr<const int32_t>(stg.buf, p_co);
+  fd.fcur_cluster = a.ptr<const int32_t>(stg.buf, p_cc);
+  fd.fcur_has = a.ptr<const uint8_t>(stg.buf, p_ch);
+  fd.emit_all = (b->flags & KAD_FOL_EMIT_ALL) ? 1 : 0;
+  fd.capacity = b->out_capacity;
+  fd.changed = a.ptr<uint8_t>(stg.buf, o_changed);
+  fd.count = a.ptr<int32_t>(stg.buf, o_count);
+  fd.fout_off = a.ptr<int64_t>(stg.buf, o_off);
+  fd.scan_sums = a.ptr<int64_t>(stg.buf, o_sums);
+  fd.out_cluster = a.ptr<int32_t>(stg.buf, o_cluster);
+  HIPCHK(c, hipEventRecord(stg.ev[0], c->stream));
+  HIPCHK(c, launch_follower_union(fd, route, c->stream));
+  HIPCHK(c, hipEventRecord(stg.ev[1], c->stream));
+  HIPCHK(c, launch_follower_scan(fd, c->stream));
+  HIPCHK(c, launch_follower_emit(fd, route, c->stream));
+  HIPCHK(c, hipEventRecord(stg.ev[2], c->stream));
+  stg.ran = true;
+  c->fol_route = route;
+  HIPCHK(c, hipMemcpyAsync(out->changed, fd.changed, f, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(out->count, fd.count, 4 * f, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(out->out_off, fd.fout_off, 8 * (f + 1), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const int64_t n_out = out->out_off[F];
+  if (n_out > b->out_capacity)
+    return fail(c, KAD_ENOSPC, "out_capacity " + std::to_string(b->out_capacity) + " < " + std::to_string(n_out) +
+                                   " emitted ids: retry with out_off[n_followers] slots");
+  if (n_out) {
+    HIPCHK(c, hipMemcpyAsync(out->out_cluster, fd.out_cluster, 4 * (size_t)n_out, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  return KAD_OK;
+}
+
+int kad_follower_check(const kad_follower_batch* b, const kad_follower_view* out, int32_t n_clusters, int32_t n_units) {
+  try {
+    if (!b || n_clusters < 0) return KAD_EINVAL;
+    if (!b->lead_off && n_units < 0) return KAD_ESTATE;
+    std::string err;
+    return validate_follower(b, out, n_clusters, b->lead_off ? 0 : n_units, &err);
+  } catch (...) {
+    return KAD_EHOST;
+  }
+}
+
+int kad_follower_union(kad_ctx* c, const kad_follower_batch* b, const kad_follower_view* out) {
+  return entry(c, b != nullptr, [&]() -> int {
+    return follower_union_locked(c, b, out);
+  });
+}
+
+int kad_follower_timing(kad_ctx* c, float ms[2]) {
+  return entry(c, ms != nullptr, [&] { return stage_timing(c, c->stage[STG_FOLLOWER], 2, ms, "no kad_follower_union ran"); });
+}
+
+int kad_follower_route_eval(int32_t n_ids, int32_t n_followers, int32_t n_cu, int32_t* out) {
+  if (!out || n_ids < 0 || n_ids > FOL_MAX_IDS || n_followers < 0 || n_cu < 1) return KAD_EINVAL;
+  const FollowerRoute r = route_follower(n_ids, n_followers, n_cu);
+  static_assert(sizeof r == 4 * KAD_FOL_ROUTE_FIELDS, "kad_follower_route_eval's record");
+  memcpy(out, &r, sizeof r);
+  return KAD_OK;
+}
+
+int kad_follower_last_route(kad_ctx* c, int32_t* out) {
+  return entry(c, out != nullptr, [&]() -> int {
+    if (!c->stage[STG_FOLLOWER].ran) return fail(c, KAD_ESTATE, "no kad_follower_union ran");
+    memcpy(out, &c->fol_route, sizeof c->fol_route);
+    return KAD_OK;
+  });
+}
+
+}  // extern "C"

@@ -81,9 +81,4 @@ inline MigrateRoute route_migrate(int S, int64_t P, int n_long, int O, int n_cu)
   return r;
 }
 
-// uns / next_cross / cap per segment (group path, then the listed long segments)
-hipError_t launch_migrate_segments(const MigrateDev& d, const MigrateRoute& r, hipStream_t st);
-// changed / n_written / retry_after / backoff per object
-hipError_t launch_migrate_objects(const MigrateDev& d, const MigrateRoute& r, hipStream_t st);
-
 }  // namespace kad

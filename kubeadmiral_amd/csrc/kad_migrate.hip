@@ -234,3 +234,216 @@ hipError_t launch_migrate_objects(const MigrateDev& d, const MigrateRoute& r, hi
 }
 
 }  // namespace kad
+
+// ------------------------------------------------------ host half: kad_migrate_*
+#include "kad_arena.h"
+
+using namespace kad;
+
+extern "C" {
+
+// ------------------------------------------------------ auto-migration
+// Every offset array monotone from 0 and ending at its count, every id in [0, n_ids) and strictly ascending
+// within its object, every flag known, every time inside the domain: all of it on the host, before anything is
+// copied or launched. With seg_obj / long_list (kad_migrate_estimate) the same pass leaves the object of
+// every segment and the segments of the long path (not skipped, more than long_min pods), ascending.
+static int validate_migrate(const kad_migrate_batch* b, const kad_migrate_view* out, int C, int long_min,
+                            std::vector<int32_t>* seg_obj, std::vector<int32_t>* long_list, std::string* err) {
+  auto bad = [&](const char* m) {
+    *err = m;
+    return KAD_EINVAL;
+  };
+  const int64_t n_ids = b->n_ids, O = b->n_objects, S = b->n_segments, P = b->n_pods, N = b->n_old;
+  constexpr int64_t TMAX = KAD_MIG_TIME_MAX;
+  if (n_ids < C || n_ids > MIG_MAX_IDS) return bad("n_ids must lie in [the snapshot's clusters, 131072]");
+  if (O < 0 || S < 0 || P < 0 || N < 0) return bad("negative count");
+  if (b->now_ns < 0 || b->now_ns > TMAX) return bad("now_ns outside [0, 2^61]");
+  if (!b->obj_seg_off || !b->old_off || !b->seg_pod_off) return bad("offset array missing");
+  if ((O && !b->obj_threshold_ns) || (S && (!b->seg_cluster || !b->seg_desired || !b->seg_flags)) ||
+      (P && (!b->pod_t_ns || !b->pod_flags)) || (N && (!b->old_cluster || !b->old_cap)))
+    return bad("input array missing");
+  {
+    const int32_t *so = b->obj_seg_off, *oo = b->old_off;
+    if (off_bad(so, O) || off_bad(oo, O)) return bad("obj_seg_off / old_off not monotone from 0");
+    if (so[O] != S || oo[O] != N) return bad("obj_seg_off / old_off does not end at n_segments / n_old");
+    const int64_t* po = b->seg_pod_off;
+    if (po[0] != 0 || first_bad(S, [&](int64_t i) { return po[i + 1] < po[i] || po[i + 1] - po[i] > INT32_MAX; }) >= 0)
+      return bad("seg_pod_off not monotone from 0, or a segment of more than 2^31 - 1 pods");
+    if (po[S] != P) return bad("seg_pod_off does not end at n_pods");
+  }
+  {
+    const int64_t* th = b->obj_threshold_ns;
+    if (first_bad(O, [&](int64_t i) { return th[i] < -TMAX || th[i] > TMAX; }) >= 0)
+      return bad("obj_threshold_ns beyond 2^61 in magnitude");
+    // ids in range and strictly ascending within each object, on both sides
+    const int32_t *so = b->obj_seg_off, *sc = b->seg_cluster, *oo = b->old_off, *oc = b->old_cluster;
+    auto asc_bad = [&](const int32_t* off, const int32_t* id, int64_t i) {
+      for (int32_t j = off[i]; j < off[i + 1]; ++j)
+        if (id[j] < 0 || id[j] >= n_ids || (j > off[i] && id[j] <= id[j - 1])) return true;
+      return false;
+    };
+    if (first_bad(O, [&](int64_t i) { return asc_bad(so, sc, i); }) >= 0)
+      return bad("seg_cluster out of range or not strictly ascending within an object");
+    if (first_bad(O, [&](int64_t i) { return asc_bad(oo, oc, i); }) >= 0)
+      return bad("old_cluster out of range or not strictly ascending within an object");
+    const uint8_t* sf = b->seg_flags;
+    if (first_bad(S, [&](int64_t i) {
+          return (sf[i] & ~(KAD_MIG_SEG_SKIP | KAD_MIG_SEG_BACKOFF)) || ((sf[i] & KAD_MIG_SEG_BACKOFF) && !(sf[i] & KAD_MIG_SEG_SKIP));
+        }) >= 0)
+      return bad("seg_flags: unknown flag, or BACKOFF without SKIP");
+    const uint8_t* pf = b->pod_flags;
+    const int64_t* pt = b->pod_t_ns;
+    if (first_bad(P, [&](int64_t i) {
+          if (pf[i] & ~(KAD_MIG_POD_DELETING | KAD_MIG_POD_UNSCHED | KAD_MIG_POD_TZERO)) return true;
+          return !(pf[i] & KAD_MIG_POD_TZERO) && (pt[i] < -TMAX || pt[i] > TMAX);
+        }) >= 0)
+      return bad("pod_flags: unknown flag, or pod_t_ns beyond 2^61 in magnitude");
+  }
+  if (!out || (S && (!out->uns || !out->next_cross || !out->cap)) ||
+      (O && (!out->changed || !out->n_written || !out->retry_after || !out->backoff)))
+    return bad("output view missing");
+  if (seg_obj) {
+    seg_obj->resize((size_t)S);
+    int32_t* so = seg_obj->data();
+    const int32_t* off = b->obj_seg_off;
+    host_parallel((int)O, [&](int lo, int hi) {
+      for (int i = lo; i < hi; ++i)
+        for (int32_t j = off[i]; j < off[i + 1]; ++j) so[j] = i;
+    });
+  }
+  if (long_list) {
+    long_list->clear();
+    const int64_t* po = b->seg_pod_off;
+    const uint8_t* sf = b->seg_flags;
+    for (int64_t i = 0; i < S; ++i)
+      if (po[i + 1] - po[i] > long_min && !(sf[i] & KAD_MIG_SEG_SKIP)) long_list->push_back((int32_t)i);
+  }
+  return KAD_OK;
+}
+
+static int migrate_estimate_locked(kad_ctx* c, const kad_migrate_batch* b, const kad_migrate_view* out) {
+  if (!c->have_snapshot) return fail(c, KAD_ESTATE, "a snapshot must be uploaded first");
+  const int long_min = c->mig_force_long_min > 0 ? c->mig_force_long_min : MIG_LONG_MIN;
+  std::string err;
+  std::vector<int32_t> seg_obj, long_list;
+  if (int r = validate_migrate(b, out, c->sd.C, long_min, &seg_obj, &long_list, &err)) return fail(c, r, err);
+  const int O = b->n_objects, S = b->n_segments, N = b->n_old;
+  const int64_t P = b->n_pods;
+  if (O == 0) return KAD_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  MigrateRoute route = route_migrate(S, P, (int)long_list.size(), O, n_cus());
+  if (c->mig_force_width > 0) {
+    route.width = c->mig_force_width;
+    const int64_t per = 256 / route.width, want = ((int64_t)S + per - 1) / per, cap = (int64_t)n_cus() * 8;
+    route.grid = (int32_t)(want < cap ? want : cap);
+    route.stride = (int32_t)(route.grid * per);
+  }
+  route.long_min = long_min;
+  // one buffer: the inputs, then the outputs
+  const size_t o = (size_t)O, sg = (size_t)S, pd = (size_t)P, n = (size_t)N, nl = long_list.size();
+  Arena a;
+  const Part p_so = a.in(b->obj_seg_off, 4 * (o + 1)), p_th = a.in(b->obj_threshold_ns, 8 * o),
+             p_sj = a.in(seg_obj.data(), 4 * sg), p_sc = a.in(b->seg_cluster, 4 * sg), p_sd = a.in(b->seg_desired, 8 * sg),
+             p_sf = a.in(b->seg_flags, sg), p_po = a.in(b->seg_pod_off, 8 * (sg + 1)), p_pt = a.in(b->pod_t_ns, 8 * pd),
+             p_pf = a.in(b->pod_flags, pd), p_ll = a.in(long_list.data(), 4 * nl), p_oo = a.in(b->old_off, 4 * (o + 1)),
+             p_oc = a.in(b->old_cluster, 4 * n), p_ov = a.in(b->old_cap, 8 * n);
+  const Part o_uns = a.out(4 * sg), o_next = a.out(8 * sg), o_cap = a.out(8 * sg), o_changed = a.out(o),
+             o_written = a.out(4 * o), o_retry = a.out(8 * o), o_backoff = a.out(o);
+  Stage& stg = c->stage[STG_MIGRATE];
+  if (int r = a.commit(c, stg.buf)) return r;
+  MigrateDev md{};
+  md.O = O;
+  md.S = S;
+  md.now = b->now_ns;
+  md.width = route.width;
+  md.obj_width = route.obj_width;
+  md.long_min = route.long_min;
+  md.n_long = (int)nl;
+  md.obj_seg_off = a.ptr<const int32_t>(stg.buf, p_so);
+  md.obj_thr = a.ptr<const int64_t>(stg.buf, p_th);
+  md.seg_obj = a.ptr<const int32_t>(stg.buf, p_sj);
+  md.seg_cluster = a.ptr<const int32_t>(stg.buf, p_sc);
+  md.seg_desired = a.ptr<const int64_t>(stg.buf, p_sd);
+  md.seg_flags = a.ptr<const uint8_t>(stg.buf, p_sf);
+  md.seg_pod_off = a.ptr<const int64_t>(stg.buf, p_po);
+  md.pod_t = a.ptr<const int64_t>(stg.buf, p_pt);
+  md.pod_flags = a.ptr<const uint8_t>(stg.buf, p_pf);
+  md.long_list = a.ptr<const int32_t>(stg.buf, p_ll);
+  md.old_off = a.ptr<const int32_t>(stg.buf, p_oo);
+  md.old_cluster = a.ptr<const int32_t>(stg.buf, p_oc);
+  md.old_cap = a.ptr<const int64_t>(stg.buf, p_ov);
+  md.uns = a.ptr<int32_t>(stg.buf, o_uns);
+  md.next_cross = a.ptr<int64_t>(stg.buf, o_next);
+  md.cap = a.ptr<int64_t>(stg.buf, o_cap);
+  md.changed = a.ptr<uint8_t>(stg.buf, o_changed);
+  md.n_written = a.ptr<int32_t>(stg.buf, o_written);
+  md.retry_after = a.ptr<int64_t>(stg.buf, o_retry);
+  md.backoff = a.ptr<uint8_t>(stg.buf, o_backoff);
+  HIPCHK(c, hipEventRecord(stg.ev[0], c->stream));
+  HIPCHK(c, launch_migrate_segments(md, route, c->stream));
+  HIPCHK(c, hipEventRecord(stg.ev[1], c->stream));
+  HIPCHK(c, launch_migrate_objects(md, route, c->stream));
+  HIPCHK(c, hipEventRecord(stg.ev[2], c->stream));
+  stg.ran = true;
+  c->mig_route = route;
+  if (S) {
+    HIPCHK(c, hipMemcpyAsync(out->uns, md.uns, 4 * sg, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out->next_cross, md.next_cross, 8 * sg, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out->cap, md.cap, 8 * sg, hipMemcpyDeviceToHost, c->stream));
+  }
+  HIPCHK(c, hipMemcpyAsync(out->changed, md.changed, o, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(out->n_written, md.n_written, 4 * o, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(out->retry_after, md.retry_after, 8 * o, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(out->backoff, md.backoff, o, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return KAD_OK;
+}
+
+int kad_migrate_check(const kad_migrate_batch* b, const kad_migrate_view* out, int32_t n_clusters) {
+  try {
+    if (!b || n_clusters < 0) return KAD_EINVAL;
+    std::string err;
+    return validate_migrate(b, out, n_clusters, MIG_LONG_MIN, nullptr, nullptr, &err);
+  } catch (...) {
+    return KAD_EHOST;
+  }
+}
+
+int kad_migrate_estimate(kad_ctx* c, const kad_migrate_batch* b, const kad_migrate_view* out) {
+  return entry(c, b != nullptr, [&]() -> int {
+    return migrate_estimate_locked(c, b, out);
+  });
+}
+
+int kad_migrate_timing(kad_ctx* c, float ms[2]) {
+  return entry(c, ms != nullptr, [&] { return stage_timing(c, c->stage[STG_MIGRATE], 2, ms, "no kad_migrate_estimate ran"); });
+}
+
+int kad_migrate_route_eval(int32_t n_segments, int64_t n_pods, int32_t n_long, int32_t n_objects, int32_t n_cu,
+                           int32_t* out) {
+  if (!out || n_segments < 0 || n_pods < 0 || n_long < 0 || n_long > n_segments || n_objects < 0 || n_cu < 1)
+    return KAD_EINVAL;
+  const MigrateRoute r = route_migrate(n_segments, n_pods, n_long, n_objects, n_cu);
+  static_assert(sizeof r == 4 * KAD_MIG_ROUTE_FIELDS, "kad_migrate_route_eval's record");
+  memcpy(out, &r, sizeof r);
+  return KAD_OK;
+}
+
+int kad_migrate_last_route(kad_ctx* c, int32_t* out) {
+  return entry(c, out != nullptr, [&]() -> int {
+    if (!c->stage[STG_MIGRATE].ran) return fail(c, KAD_ESTATE, "no kad_migrate_estimate ran");
+    memcpy(out, &c->mig_route, sizeof c->mig_route);
+    return KAD_OK;
+  });
+}
+
+int kad_migrate_debug_route(kad_ctx* c, int32_t force_width, int32_t force_long_min) {
+  const bool width_ok = force_width == 0 || force_width == 8 || force_width == 16 || force_width == 32 || force_width == 64;
+  return entry(c, force_long_min >= 0 && width_ok, [&]() -> int {
+    c->mig_force_width = force_width;
+    c->mig_force_long_min = force_long_min;
+    return KAD_OK;
+  });
+}
+
+}  // extern "C"

@@ -213,3 +213,285 @@ hipError_t launch_override_match(const OverrideDev& o, hipStream_t st) {
 }
 
 }  // namespace kad
+
+// ------------------------------------------------------ host half: kad_override_*
+#include "kad_arena.h"
+
+using namespace kad;
+
+// ------------------------------------------------------ override policies
+// A policy-set blob may come from any packer: before it is copied to the device every array is checked to
+// lie in the blob, every CSR offset array to be monotone, every id the kernels index with to be in range
+// and every target program to be well formed. Host only: sh is the header of the snapshot it was packed for.
+static int validate_policies(const void* blob, size_t nbytes, const kad_snapshot_header& sh, kad_override_header* hdr,
+                             std::string* err) {
+  auto bad = [&](const std::string& m) {
+    *err = m;
+    return KAD_EINVAL;
+  };
+  kad_override_header h;
+  if (!blob || nbytes < sizeof(h)) return bad("policy set too small");
+  std::memcpy(&h, blob, sizeof(h));
+  if (h.magic != KAD_OVERRIDE_MAGIC) return bad("bad policy set magic");
+  if (h.abi_version != KAD_ABI_VERSION) return bad("policy set ABI version mismatch");
+  if (h.total_bytes != nbytes) return bad("policy set size mismatch");
+  if (h.snapshot_fingerprint != sh.fingerprint || h.n_clusters != sh.n_clusters)
+    return bad("policy set was packed against a different snapshot");
+  const int P = h.n_policies, R = h.n_rules, NR = h.n_reqs, C = sh.n_clusters, K = sh.n_label_keys;
+  if (P < 0 || R < 0 || NR < 0) return bad("bad policy set counts");
+  const char* base = static_cast<const char*>(blob);
+  auto extent = [&](int a, uint64_t count) {
+    const uint64_t o = h.off[a];
+    return o <= nbytes && !(o & 7) && count <= (nbytes - o) / 4;
+  };
+  auto arr = [&](int a) { return reinterpret_cast<const int32_t*>(base + h.off[a]); };
+  // offsets off_a[0 .. n]: from 0, non-decreasing; the data array holds off[n] words
+  auto csr = [&](int off_a, int n, int data_a) {
+    if (!extent(off_a, (uint64_t)n + 1)) return false;
+    const int32_t* o = arr(off_a);
+    if (o[0] != 0) return false;
+    for (int i = 0; i < n; i++)
+      if (o[i + 1] < o[i]) return false;
+    return data_a < 0 || extent(data_a, (uint64_t)o[n]);
+  };
+  if (!csr(KAD_O_POL_RULE_OFF, P, -1) || arr(KAD_O_POL_RULE_OFF)[P] != R)
+    return bad("policy rule offsets must run from 0 to n_rules");
+  if (!extent(KAD_O_RULE_FLAGS, (uint64_t)R)) return bad("policy set array rule_flags lies outside the blob");
+  if (!csr(KAD_O_RULE_NAME_OFF, R, KAD_O_RULE_NAME)) return bad("bad rule name offsets");
+  if (!csr(KAD_O_RULE_PROG_OFF, R, KAD_O_RULE_PROG)) return bad("bad rule program offsets");
+  if (!csr(KAD_O_REQ_OFF, NR, KAD_O_REQ)) return bad("bad requirement offsets");
+  const uint32_t* fl = reinterpret_cast<const uint32_t*>(arr(KAD_O_RULE_FLAGS));
+  const int32_t *no = arr(KAD_O_RULE_NAME_OFF), *nm = arr(KAD_O_RULE_NAME);
+  const int32_t *po = arr(KAD_O_RULE_PROG_OFF), *pg = arr(KAD_O_RULE_PROG);
+  const int32_t *ro = arr(KAD_O_REQ_OFF), *rq = arr(KAD_O_REQ);
+  for (int r = 0; r < NR; r++) {  // [op | n << 8, key, payload...], as validate_batch
+    const int len = ro[r + 1] - ro[r];
+    if (len < 2) return bad("requirement shorter than two words");
+    const int32_t* p = rq + ro[r];
+    const int op = p[0] & 0xff, n = (int)((uint32_t)p[0] >> 8), key = p[1];
+    if (len != 2 + n) return bad("requirement payload length mismatch");
+    const bool label_key = key >= 0 && key < K;
+    bool ok;
+    switch (op) {
+      case KAD_OP_IN: case KAD_OP_NOTIN: case KAD_OP_EQ: ok = label_key && n >= 1; break;
+      case KAD_OP_EXISTS: case KAD_OP_DNE: ok = label_key && n == 0; break;
+      case KAD_OP_GT: case KAD_OP_LT: ok = label_key && n == 2; break;
+      case KAD_OP_NAME_EQ: case KAD_OP_NAME_NE: ok = key >= -1 && key < C; break;
+      case KAD_OP_TRUE: case KAD_OP_FALSE: ok = true; break;
+      default: ok = false;
+    }
+    if (!ok) return bad("bad requirement " + std::to_string(r));
+  }
+  for (int r = 0; r < R; r++) {
+    if (fl[r] & ~(KAD_OVR_HAS_TARGET | KAD_OVR_HAS_NAMES | KAD_OVR_SEL_INVALID | KAD_OVR_BAD_VALUE))
+      return bad("unknown flags of rule " + std::to_string(r));
+    for (int j = no[r]; j < no[r + 1]; j++)
+      if (nm[j] < 0 || nm[j] >= C || (j > no[r] && nm[j] <= nm[j - 1]))
+        return bad("cluster ids of rule " + std::to_string(r) + " must be ascending snapshot ids");
+    // the program: every requirement id in range, the structure consumes exactly the rule's words
+    const int32_t* p = pg + po[r];
+    const int64_t len = po[r + 1] - po[r];
+    auto ids_ok = [&](int64_t at, int64_t n) {
+      if (n < 0 || at + n > len) return false;
+      for (int64_t i = 0; i < n; i++)
+        if (p[at + i] < 0 || p[at + i] >= NR) return false;
+      return true;
+    };
+    bool ok = len >= 2;
+    int64_t pc = 0;
+    if (ok) {
+      const int64_t n_sel = p[pc++];
+      ok = ids_ok(pc, n_sel);
+      pc += ok ? n_sel : 0;
+      ok = ok && pc < len;
+      if (ok && p[pc++]) {
+        ok = pc < len;
+        const int64_t n_terms = ok ? p[pc++] : 0;
+        ok = ok && n_terms >= 0;
+        for (int64_t t = 0; ok && t < n_terms; t++) {
+          ok = pc + 3 <= len;
+          if (!ok) break;
+          const int64_t ne = p[pc + 1], nf = p[pc + 2];
+          ok = ne >= 0 && nf >= 0 && ids_ok(pc + 3, ne + nf);
+          pc += 3 + (ok ? ne + nf : 0);
+        }
+      }
+    }
+    if (!ok || pc != len) return bad("malformed target program of rule " + std::to_string(r));
+  }
+  *hdr = h;
+  return KAD_OK;
+}
+
+static int override_policies_upload_locked(kad_ctx* c, const void* blob, size_t nbytes) {
+  c->have_ovr = false;  // a failed upload leaves no policy set resident
+  if (!c->have_snapshot) return fail(c, KAD_ESTATE, "no snapshot uploaded");
+  kad_override_header h;
+  std::string err;
+  if (int r = validate_policies(blob, nbytes, c->snap_hdr, &h, &err)) return fail(c, r, err);
+  HIPCHK(c, hipSetDevice(c->device));
+  if (int r = grow(c, c->d_ovr, nbytes)) return r;
+  HIPCHK(c, hipMemcpyAsync(c->d_ovr.p, blob, nbytes, hipMemcpyHostToDevice, c->stream));
+  const int32_t* pro = at<int32_t>(blob, h.off, KAD_O_POL_RULE_OFF);
+  c->h_ovr_pro.assign(pro, pro + h.n_policies + 1);
+  const size_t nch = (size_t)((c->sd.C + 63) / 64);
+  const ReqRouting rr = route_requirements(h.n_reqs, at<int32_t>(blob, h.off, KAD_O_REQ_OFF),
+                                           at<int32_t>(blob, h.off, KAD_O_REQ), c->snap_hdr.n_label_keys, nch,
+                                           c->sd.vrows != nullptr, c->h_ovr_reqseg);
+  c->ovr_n_seg = rr.n_seg;
+  c->ovr_n_rowreq = rr.n_rowreq;
+  c->ovr_n_seg_reqs = rr.n_seg_reqs;
+  if (int r = grow(c, c->d_ovr_reqseg, c->h_ovr_reqseg.size() * 4 + 16)) return r;
+  if (!c->h_ovr_reqseg.empty())
+    HIPCHK(c, hipMemcpyAsync(c->d_ovr_reqseg.p, c->h_ovr_reqseg.data(), c->h_ovr_reqseg.size() * 4, hipMemcpyHostToDevice,
+                             c->stream));
+  if (int r = grow(c, c->d_ovr_rows, ((size_t)h.n_reqs + 2 * (size_t)h.n_rules) * nch * 8)) return r;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->ovr_hdr = h;
+  c->have_ovr = true;
+  return KAD_OK;
+}
+
+static int override_match_locked(kad_ctx* c, const kad_override_batch* b, const kad_override_view* out) {
+  if (!c->have_snapshot || !c->have_ovr) return fail(c, KAD_ESTATE, "snapshot and policy set must be uploaded first");
+  const bool from_results = b->place_off == nullptr;
+  if (from_results && (!c->have_batch || !c->ran)) return fail(c, KAD_ESTATE, "nothing has been scheduled");
+  const kad_override_header& h = c->ovr_hdr;
+  const int n = b->n_objects, RW = b->rule_words, P = h.n_policies, C = c->sd.C;
+  if (n < 0 || RW < 1 || (n && (!b->obj_policy || !out || !out->status)))
+    return fail(c, KAD_EINVAL, "object list or output view missing");
+  if (from_results && n != c->bd.W) return fail(c, KAD_EINVAL, "n_objects differs from the resident batch's units");
+  if (!from_results && (b->place_off[0] != 0 || (b->place_off[n] && !b->place_cluster)))
+    return fail(c, KAD_EINVAL, "place_off must start at 0");
+  const int32_t* pro = c->h_ovr_pro.data();
+  {
+    const int32_t* op = b->obj_policy;
+    const int64_t i = first_bad(n, [&](int64_t i) {
+      int64_t rules = 0;
+      for (int q = 0; q < 2; q++) {
+        const int p = op[2 * i + q];
+        if (p < -1 || p >= P) return true;
+        if (p >= 0) rules += pro[p + 1] - pro[p];
+      }
+      return rules > 32 * (int64_t)RW;
+    });
+    if (i >= 0)
+      return fail(c, KAD_EINVAL, "object " + std::to_string(i) + ": policy index out of range, or more than 32 * rule_words rules");
+  }
+  int64_t n_slots;
+  if (from_results) {
+    n_slots = c->slot_n + c->cur_n;
+  } else {
+    // (its start and a missing place_cluster were told apart above, so each check has one message)
+    if (off_bad(b->place_off, n)) return fail(c, KAD_EINVAL, "place_off must be non-decreasing");
+    n_slots = b->place_off[n];
+    if (csr_bad(b->place_off, b->place_cluster, n, -1, C)) return fail(c, KAD_EINVAL, "placed cluster id out of range");
+  }
+  if (n == 0) return KAD_OK;
+  if (n_slots && !out->matched) return fail(c, KAD_EINVAL, "output view missing");
+  HIPCHK(c, hipSetDevice(c->device));
+  // one buffer: obj_policy, place_off, place_cluster, then status and the matched rows
+  const size_t m_bytes = 4 * (size_t)n_slots * RW;
+  Arena a;
+  const Part p_op = a.in(b->obj_policy, 8 * (size_t)n),
+             p_po = from_results ? Arena::absent() : a.in(b->place_off, 4 * ((size_t)n + 1)),
+             p_pc = from_results ? Arena::absent() : a.in(b->place_cluster, 4 * (size_t)n_slots),
+             o_st = a.out(4 * (size_t)n), o_m = a.out(m_bytes);
+  Stage& stg = c->stage[STG_OVERRIDE];
+  if (int r = a.commit(c, stg.buf)) return r;
+  const size_t nch = (size_t)((C + 63) / 64);
+  const char* base = c->d_ovr.as<const char>();
+  uint64_t* rows = c->d_ovr_rows.as<uint64_t>();
+  // requirement rows of the set's table: req_row_kernel and req_mask_kernel read these fields only
+  BatchDev rb{};
+  rb.NR = h.n_reqs;
+  rb.req_off = at<int32_t>(base, h.off, KAD_O_REQ_OFF);
+  rb.req = at<int32_t>(base, h.off, KAD_O_REQ);
+  rb.req_mask = rows;
+  rb.n_seg = c->ovr_n_seg;
+  rb.req_perm = c->d_ovr_reqseg.as<const int32_t>();
+  rb.req_seg = reinterpret_cast<const int4*>(rb.req_perm + (size_t)c->ovr_n_seg_reqs * 8);
+  rb.n_rowreq = c->ovr_n_rowreq;
+  rb.req_rows = reinterpret_cast<const int4*>(reinterpret_cast<const int32_t*>(rb.req_seg) + 4 * (size_t)c->ovr_n_seg);
+  OverrideDev o{};
+  o.C = C;
+  o.P = P;
+  o.R = h.n_rules;
+  o.pol_rule_off = at<int32_t>(base, h.off, KAD_O_POL_RULE_OFF);
+  o.rule_flags = at<uint32_t>(base, h.off, KAD_O_RULE_FLAGS);
+  o.name_off = at<int32_t>(base, h.off, KAD_O_RULE_NAME_OFF);
+  o.name = at<int32_t>(base, h.off, KAD_O_RULE_NAME);
+  o.prog_off = at<int32_t>(base, h.off, KAD_O_RULE_PROG_OFF);
+  o.prog = at<int32_t>(base, h.off, KAD_O_RULE_PROG);
+  o.req_mask = rows;
+  o.M = rows + (size_t)h.n_reqs * nch;
+  o.E = o.M + (size_t)h.n_rules * nch;
+  o.n_obj = n;
+  o.RW = RW;
+  o.obj_policy = a.ptr<const int32_t>(stg.buf, p_op);
+  o.from_results = from_results ? 1 : 0;
+  if (from_results) {
+    o.out_off = c->bd.out_off;
+    o.cur_off = c->bd.cur_off;
+    o.cur_id = c->bd.cur_id;
+    o.res_status = c->d_status;
+    o.res_count = c->d_count;
+    o.res_cluster = c->d_cluster;
+    o.slot_lo = c->slot_lo;
+    o.n_out = c->slot_n;
+    o.cur_lo = c->cur_lo;
+  }
+  o.place_off = a.ptr<const int32_t>(stg.buf, p_po);
+  o.place_cluster = a.ptr<const int32_t>(stg.buf, p_pc);
+  o.n_slots = n_slots;
+  o.status = a.ptr<int32_t>(stg.buf, o_st);
+  o.matched = a.ptr<uint32_t>(stg.buf, o_m);
+  HIPCHK(c, hipEventRecord(stg.ev[0], c->stream));
+  bool zeroed = false;
+  HIPCHK(c, launch_req_masks(c->sd, rb, c->stream, false, &zeroed));
+  HIPCHK(c, hipEventRecord(stg.ev[1], c->stream));
+  HIPCHK(c, launch_override_rule_rows(o, c->stream));
+  HIPCHK(c, hipEventRecord(stg.ev[2], c->stream));
+  HIPCHK(c, launch_override_match(o, c->stream));
+  HIPCHK(c, hipEventRecord(stg.ev[3], c->stream));
+  stg.ran = true;
+  HIPCHK(c, hipMemcpyAsync(out->status, o.status, 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  if (m_bytes) HIPCHK(c, hipMemcpyAsync(out->matched, o.matched, m_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return KAD_OK;
+}
+
+extern "C" {
+
+// Host only (tests, packers): validate_policies against the header of a packed snapshot blob.
+int kad_override_policies_check(const void* blob, size_t nbytes, const void* snapshot_blob, size_t snapshot_nbytes) {
+  try {
+    kad_snapshot_header sh;
+    if (!snapshot_blob || snapshot_nbytes < sizeof(sh)) return KAD_EINVAL;
+    std::memcpy(&sh, snapshot_blob, sizeof(sh));
+    if (sh.magic != KAD_SNAPSHOT_MAGIC) return KAD_EINVAL;
+    kad_override_header h;
+    std::string err;
+    return validate_policies(blob, nbytes, sh, &h, &err);
+  } catch (...) {
+    return KAD_EHOST;
+  }
+}
+
+int kad_override_policies_upload(kad_ctx* c, const void* blob, size_t nbytes) {
+  return entry(c, blob != nullptr, [&]() -> int {
+    return override_policies_upload_locked(c, blob, nbytes);
+  });
+}
+
+int kad_override_match(kad_ctx* c, const kad_override_batch* b, const kad_override_view* out) {
+  return entry(c, b != nullptr, [&]() -> int {
+    return override_match_locked(c, b, out);
+  });
+}
+
+int kad_override_timing(kad_ctx* c, float ms[3]) {
+  return entry(c, ms != nullptr, [&] { return stage_timing(c, c->stage[STG_OVERRIDE], 3, ms, "no kad_override_match ran"); });
+}
+
+}  // extern "C"

@@ -165,3 +165,123 @@ hipError_t launch_trigger_objects(const TriggerDev& t, hipStream_t st) {
 }
 
 }  // namespace kad
+
+// ------------------------------------------------------ host half: kad_trigger_*
+#include "kad_arena.h"
+
+using namespace kad;
+
+extern "C" {
+
+/* ------------------------------------------------ scheduling-trigger hashes */
+static int trigger_suffix_upload_locked(kad_ctx* c, const uint8_t* suffix, size_t nbytes) {
+  HIPCHK(c, hipSetDevice(c->device));
+  int r = grow(c, c->t_suffix, ((nbytes + 63) & ~(size_t)63) + 64);
+  if (r) return r;
+  const int64_t ntab = trigger_table_count((int64_t)nbytes);
+  r = grow(c, c->t_tabs, (size_t)ntab * 256 * 4 + (size_t)ntab * 4 + 256);
+  if (r) return r;
+  if (nbytes) HIPCHK(c, hipMemcpyAsync(c->t_suffix.p, suffix, nbytes, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  TriggerDev& t = c->td;
+  t.suffix = c->t_suffix.as<const uint32_t>();
+  t.suffix_len = (int64_t)nbytes;
+  t.tables = c->t_tabs.as<uint32_t>();
+  t.powers = t.tables + (size_t)ntab * 256;
+  c->t_suffix_len = (int64_t)nbytes;
+  c->stage[STG_TRIGGER].ran = false;
+  return KAD_OK;
+}
+
+static int trigger_prefixes_upload_locked(kad_ctx* c, int n, const int64_t* prefix_off, const uint8_t* prefix) {
+  if (off_bad(prefix_off, n)) return fail(c, KAD_EINVAL, "prefix_off must be non-decreasing");  // (from 0: the entry's check)
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t nbytes = (size_t)prefix_off[n];
+  if (int r = grow(c, c->t_prefix, nbytes + 64)) return r;
+  Arena a;
+  const Part p_off = a.in(prefix_off, 8 * ((size_t)n + 1)), o_out = a.out(4 * (size_t)n);
+  Stage& stg = c->stage[STG_TRIGGER];
+  if (int r = a.commit(c, stg.buf)) return r;
+  if (nbytes) HIPCHK(c, hipMemcpyAsync(c->t_prefix.p, prefix, nbytes, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  TriggerDev& t = c->td;
+  t.n = n;
+  t.prefix = c->t_prefix.as<const uint8_t>();
+  t.prefix_off = a.ptr<const int64_t>(stg.buf, p_off);
+  t.out = a.ptr<uint32_t>(stg.buf, o_out);
+  c->t_n = n;
+  stg.ran = false;
+  return KAD_OK;
+}
+
+static int trigger_run_locked(kad_ctx* c) {
+  if (c->t_suffix_len < 0 || c->t_n < 0) return fail(c, KAD_ESTATE, "upload the trigger suffix and prefixes first");
+  HIPCHK(c, hipSetDevice(c->device));
+  Stage& stg = c->stage[STG_TRIGGER];
+  HIPCHK(c, hipEventRecord(stg.ev[0], c->stream));
+  HIPCHK(c, launch_trigger_summary(c->td, c->stream));
+  HIPCHK(c, hipEventRecord(stg.ev[1], c->stream));
+  HIPCHK(c, launch_trigger_objects(c->td, c->stream));
+  HIPCHK(c, hipEventRecord(stg.ev[2], c->stream));
+  stg.ran = true;
+  return KAD_OK;
+}
+
+int kad_trigger_timing(kad_ctx* c, float ms[2]) {
+  return entry(c, ms != nullptr, [&]() -> int {
+    // the whole run, then its summary part: not stage_timing's neighbouring intervals
+    const Stage& stg = c->stage[STG_TRIGGER];
+    if (!stg.ran) return fail(c, KAD_ESTATE, "no trigger run");
+    HIPCHK(c, hipEventSynchronize(stg.ev[2]));
+    HIPCHK(c, hipEventElapsedTime(&ms[0], stg.ev[0], stg.ev[2]));
+    HIPCHK(c, hipEventElapsedTime(&ms[1], stg.ev[0], stg.ev[1]));
+    return KAD_OK;
+  });
+}
+
+static int trigger_download_locked(kad_ctx* c, uint32_t* out_hash) {
+  if (!c->stage[STG_TRIGGER].ran) return fail(c, KAD_ESTATE, "no trigger run");
+  HIPCHK(c, hipSetDevice(c->device));
+  if (c->t_n > 0 && out_hash)
+    HIPCHK(c, hipMemcpyAsync(out_hash, c->td.out, (size_t)c->t_n * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return KAD_OK;
+}
+
+int kad_trigger_suffix_upload(kad_ctx* c, const uint8_t* suffix, size_t nbytes) {
+  return entry(c, suffix || !nbytes, [&]() -> int {
+    return trigger_suffix_upload_locked(c, suffix, nbytes);
+  });
+}
+
+int kad_trigger_prefixes_upload(kad_ctx* c, int n, const int64_t* prefix_off, const uint8_t* prefix) {
+  return entry(c, n >= 0 && prefix_off && prefix_off[0] == 0, [&]() -> int {
+    return trigger_prefixes_upload_locked(c, n, prefix_off, prefix);
+  });
+}
+
+int kad_trigger_run(kad_ctx* c) {
+  return entry(c, true, [&]() -> int {
+    return trigger_run_locked(c);
+  });
+}
+
+int kad_trigger_download(kad_ctx* c, uint32_t* out_hash) {
+  return entry(c, true, [&]() -> int {
+    return trigger_download_locked(c, out_hash);
+  });
+}
+
+// one critical section (see kad_schedule_batch)
+int kad_trigger_hashes(kad_ctx* c, int n, const int64_t* prefix_off, const uint8_t* prefix, const uint8_t* suffix,
+                       size_t suffix_len, uint32_t* out_hash) {
+  return entry(c, (suffix || !suffix_len) && n >= 0 && prefix_off && prefix_off[0] == 0, [&]() -> int {
+    int r = trigger_suffix_upload_locked(c, suffix, suffix_len);
+    if (!r) r = trigger_prefixes_upload_locked(c, n, prefix_off, prefix);
+    if (!r) r = trigger_run_locked(c);
+    if (!r) r = trigger_download_locked(c, out_hash);
+    return r;
+  });
+}
+
+}  // extern "C"

@@ -201,6 +201,18 @@ def test_abi_validation_without_gpu():
     assert _check(3, 2, 3, _fol(), n_leaders=2, sched=FC.csr([[0], [3]])) == EINVAL
     assert _check(3, 2, 3, _fol(), n_leaders=3, keep=FC.csr([[0], [2], [1]])) == 0
     assert _check(3, 2, 3, _fol(fol=((2,),)), n_leaders=3, keep=FC.csr([[0], [2], [1]])) == 0
+    # one malformed CSR per array the cases above leave out, each beside its well-formed twin
+    assert _check(3, -1, 3, _fol(), leaders=lead, keep=FC.csr([[0], [2]])) == 0
+    assert _check(3, -1, 3, _fol(), leaders=lead, keep=FC.csr([[0], [3]])) == EINVAL     # keep id >= n_ids
+    assert _check(3, -1, 3, _fol(), leaders=lead, keep=FC.csr([[-1], [2]])) == EINVAL    # keep id < 0
+    for off in ([1, 1, 2], [0, 2, 1]):                                               # sched_off: start, monotone
+        bad = (np.array(off, np.int32), np.array([0, 2], np.int32))
+        assert _check(3, 2, 3, _fol(), n_leaders=2, sched=bad) == EINVAL, off
+    for i in (0, 2):                                                                 # fol_off / cur_off from 1
+        f = list(_fol(fol=((0,), (1,)), cur=((0,), (1,)), has=(1, 1)))
+        assert _check(3, -1, 3, tuple(f), leaders=lead) == 0
+        f[i] = np.array([1, 1, 2], np.int32)
+        assert _check(3, -1, 3, tuple(f), leaders=lead) == EINVAL, i
 
 
 def test_follower_route_eval():

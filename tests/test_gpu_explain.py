@@ -116,6 +116,45 @@ def test_explain_matches_oracle(ctx, case, order):
     assert ((d.first_fail == NOT_REJECTED)[~sticky] == feas_dbg[~sticky].astype(bool)).all()
 
 
+def test_staging_buffer_grows_is_reused_and_shrinks():
+    """One context: 4 units on C = 3 (with both optional outputs, and with neither: two absent parts), the
+    C = 130 case per cluster (about 100x larger), the tiny ones again. Each step equals the oracle, the repeats
+    equal the first runs bit for bit; the timer reports KAD_ESTATE before the first call."""
+    from kubeadmiral_amd import runtime
+    c = runtime.Context(0)
+
+    def timing_ok():
+        ms = c.explain_timing()
+        assert len(ms) == 2 and all(np.isfinite(t) and t >= 0 for t in ms), ms
+    try:
+        fwk = framework(DEFAULT)
+        tiny, big = (6, 3, 9, 4), CASES[3]
+        clusters, units, _, _ = upload(c, tiny, fwk)
+        with pytest.raises(runtime.KadError) as e:
+            c.explain_timing()
+        assert e.value.code == runtime.KAD_ESTATE
+        want = oracle_explain(clusters, units, DEFAULT)
+        first = c.explain(fwk, per_cluster=True)
+        assert_diag(first, want)
+        timing_ok()
+        bare = c.explain(fwk, units=[2, 0], per_cluster=False, fit_detail=False)
+        assert bare.fit_detail is None and bare.first_fail is None
+        assert (bare.rejected == want[0][[2, 0]]).all() and (bare.feasible == want[1][[2, 0]]).all()
+        timing_ok()
+        upload(c, big, fwk)
+        assert_diag(c.explain(fwk, per_cluster=True), expected(big, "default"))
+        timing_ok()
+        upload(c, tiny, fwk)
+        again = c.explain(fwk, per_cluster=True)
+        for k in ("rejected", "feasible", "fit_detail", "first_fail"):
+            assert getattr(again, k).tobytes() == getattr(first, k).tobytes(), k
+        bare2 = c.explain(fwk, units=[2, 0], per_cluster=False, fit_detail=False)
+        assert bare2.rejected.tobytes() == bare.rejected.tobytes() and bare2.feasible.tobytes() == bare.feasible.tobytes()
+        timing_ok()
+    finally:
+        c.close()
+
+
 def test_inputs_cover_every_plugin_and_fit_reason():
     """The fuzz inputs exercise what the kernel distinguishes: every plugin is a first failure, every Fit
     resource is short somewhere, and many units have no feasible cluster."""

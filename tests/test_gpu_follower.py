@@ -130,6 +130,65 @@ def test_resident_mode(ctx):
     assert (again.status == res.status).all() and (again.cluster == res.cluster).all()
 
 
+def _assert_timing(ms):
+    assert len(ms) >= 2 and all(np.isfinite(t) and t >= 0 for t in ms), ms
+
+
+def test_staging_buffer_grows_is_reused_and_shrinks():
+    """One context: a tiny batch with empty and absent parts (a follower without leaders or current clusters, no
+    current cluster anywhere, no keep / sched), one about 100x larger, the tiny one again. Each step equals the
+    checker, the third equals the first bit for bit; the timer reports KAD_ESTATE before the first call."""
+    from kubeadmiral_amd import runtime
+    c = runtime.Context(0)
+    try:
+        c.upload_snapshot(small_snapshot(3))
+        with pytest.raises(runtime.KadError) as e:
+            c.follower_timing()
+        assert e.value.code == runtime.KAD_ESTATE
+        rows = [[0, 1], [2], []]
+        tiny = (FC.csr([[0, 1], [], [1, 2]]) + (np.zeros(4, np.int32), np.zeros(0, np.int32), np.array([0, 0, 1], np.uint8)))
+        want = R.union_batch(tiny, [set(r) for r in rows])
+        first = c.follower_union(3, tiny, leaders=FC.csr(rows))
+        assert_equal(first, want)
+        assert first["changed"].tolist() == [1, 0, 1] and first["count"].tolist() == [3, 0, 1]
+        _assert_timing(c.follower_timing())
+        lead, sets, fol, _ = FC.explicit_case(4100)
+        assert len(lead[1]) >= 100 * 3  # leader ids: the tiny batch has 3
+        assert_equal(c.follower_union(4100, fol, leaders=lead), R.union_batch(fol, sets))
+        _assert_timing(c.follower_timing())
+        again = c.follower_union(3, tiny, leaders=FC.csr(rows))
+        assert_equal(again, want)
+        for k in ("changed", "count", "out_off", "out_cluster"):
+            assert again[k].tobytes() == first[k].tobytes(), k
+        _assert_timing(c.follower_timing())
+    finally:
+        c.close()
+
+
+def test_staging_buffer_resident_mode_small_large_small(ctx):
+    """Resident mode on one context: without keep / sched (both parts absent) and no follower at all but one
+    without leaders, then the full resident case, then the first again, bit for bit."""
+    snap, fwk, batch, n_ids, L, keep, sched, fol = FC.resident_case()
+    ctx.upload_snapshot(snap)
+    res = ctx.run(fwk, batch)
+    hdr = pack.header_of(batch.blob, pack.BatchHeader)
+    cur_off = pack.array_of(batch.blob, hdr, pack.B_CUR_OFF, np.int32, hdr.n_units + 1)
+    cur_id = pack.array_of(batch.blob, hdr, pack.B_CUR_ID, np.int32, int(cur_off[-1]))
+    sets0 = R.resident_leader_sets(res.status, res.count, res.cluster, batch.out_off, cur_off, cur_id, L, None, None)
+    tiny = (FC.csr([[0], [], [1, 0]]) + (np.zeros(4, np.int32), np.zeros(0, np.int32), np.zeros(3, np.uint8)))
+    want = R.union_batch(tiny, sets0)
+    first = ctx.follower_union(n_ids, tiny, n_leaders=L)
+    assert_equal(first, want)
+    _assert_timing(ctx.follower_timing())
+    sets = R.resident_leader_sets(res.status, res.count, res.cluster, batch.out_off, cur_off, cur_id, L, sched, keep)
+    assert_equal(ctx.follower_union(n_ids, fol, keep=keep, sched=sched, n_leaders=L), R.union_batch(fol, sets))
+    _assert_timing(ctx.follower_timing())
+    again = ctx.follower_union(n_ids, tiny, n_leaders=L)
+    for k in ("changed", "count", "out_off", "out_cluster"):
+        assert again[k].tobytes() == first[k].tobytes(), k
+    _assert_timing(ctx.follower_timing())
+
+
 def _pod_template(rng, w):
     spec = {"containers": [{"name": "c", "envFrom": [{"configMapRef": {"name": f"cm-{int(rng.integers(0, 40))}"}}],
                             "env": [{"name": "E", "valueFrom": {"secretKeyRef": {"name": f"sec-{int(rng.integers(0, 40))}", "key": "k"}}}]}],

@@ -64,6 +64,46 @@ def assert_equal(got, want):
         assert g == want[k], (k, [i for i, (a, b) in enumerate(zip(g, want[k])) if a != b][:5])
 
 
+def test_staging_buffer_grows_is_reused_and_shrinks(long_min):
+    """One context: a tiny batch with empty parts (an object with zero segments, a segment without pods, no old
+    entry, no long segment), the shapes batch (about 100x larger), the tiny one again. Each step equals the
+    checker, the third equals the first bit for bit; the timer reports KAD_ESTATE before the first call."""
+    from kubeadmiral_amd import runtime
+    c = runtime.Context(0)
+    try:
+        clusters, _ = synth.gen_fuzz(11, W=1, C=3)
+        c.upload_snapshot(pack.Snapshot(clusters))
+        with pytest.raises(runtime.KadError) as e:
+            c.migrate_timing()
+        assert e.value.code == runtime.KAD_ESTATE
+        b = MC.Builder(n_ids=3)
+        U = R.POD_UNSCHED
+        b.add(60 * MC.SEC, [], "empty")                                                        # zero segments
+        b.add(60 * MC.SEC, [(0, 2, 0, [(U, MC.NOW - 61 * MC.SEC), (U, MC.NOW - 59 * MC.SEC)]), (2, 1, 0, [])], "empty")
+        b.add(0, [(1, 3, 0, [(U, MC.NOW), (0, MC.NOW)])], "empty")
+        tiny = b.arrays()
+        assert len(tiny["old_cluster"]) == 0 and len(tiny["obj_threshold_ns"]) == 3
+        want = R.run(**tiny)
+        first = c.migrate_estimate(**tiny)
+        assert_equal(first, want)
+        _timing_ok(c.migrate_timing())
+        arr, _, big_want = shapes(long_min, 64)
+        assert len(arr["pod_t_ns"]) >= 100 * len(tiny["pod_t_ns"])
+        assert_equal(c.migrate_estimate(**arr), big_want)
+        _timing_ok(c.migrate_timing())
+        again = c.migrate_estimate(**tiny)
+        assert_equal(again, want)
+        for k in KEYS:
+            assert np.asarray(again[k]).tobytes() == np.asarray(first[k]).tobytes(), k
+        _timing_ok(c.migrate_timing())
+    finally:
+        c.close()
+
+
+def _timing_ok(ms):
+    assert len(ms) >= 2 and all(np.isfinite(t) and t >= 0 for t in ms), ms
+
+
 @pytest.mark.parametrize("width", [64, 32, 16, 8])
 def test_shapes_parity(ctx, long_min, width):
     arr, marks, want = shapes(long_min, width)

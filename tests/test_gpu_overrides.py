@@ -203,6 +203,96 @@ def test_placed_clusters_from_results(ctx):
         assert a.tobytes() == b.tobytes()
 
 
+def _timing_ok(ms):
+    assert len(ms) == 3 and all(np.isfinite(t) and t >= 0 for t in ms), ms
+
+
+def test_staging_buffer_explicit_small_large_small():
+    """One context, explicit placements: 3 objects on C = 3 with n_slots = 0 and with their own placements, the
+    200-object C = 65 case, the tiny ones again. Each step equals the checker, the repeats equal the first runs
+    bit for bit; the timer reports KAD_ESTATE before the first call."""
+    from kubeadmiral_amd import runtime
+    c = runtime.Context(0)
+    try:
+        clusters, snap, pols, op, off, ids, rw, status, rows = inputs(6, 3, 3)
+        upload(c, snap, pols)
+        with pytest.raises(runtime.KadError) as e:
+            c.override_timing()
+        assert e.value.code == runtime.KAD_ESTATE
+        off0, ids0 = np.zeros(len(op) + 1, np.int32), np.zeros(0, np.int32)
+        status0, rows0 = R.expected_match(pols, op, off0, ids0, clusters, rw)
+        first0 = c.override_match(op, (off0, ids0), rule_words=rw)
+        assert (first0[0] == status0).all() and len(first0[1]) == 0 == len(rows0)
+        _timing_ok(c.override_timing())
+        first = c.override_match(op, (off, ids), rule_words=rw)
+        assert (first[0] == status).all() and (first[1] == rows).all()
+        _, bsnap, bpols, bop, boff, bids, brw, bstatus, brows = inputs(3, 65)
+        assert len(bids) >= 30 * max(1, len(ids))
+        upload(c, bsnap, bpols)
+        big = c.override_match(bop, (boff, bids), rule_words=brw)
+        assert (big[0] == bstatus).all() and (big[1] == brows).all()
+        _timing_ok(c.override_timing())
+        upload(c, snap, pols)
+        for want, placed in ((first0, (off0, ids0)), (first, (off, ids))):
+            again = c.override_match(op, placed, rule_words=rw)
+            assert again[0].tobytes() == want[0].tobytes() and again[1].tobytes() == want[1].tobytes()
+            _timing_ok(c.override_timing())
+    finally:
+        c.close()
+
+
+def _results_case(W, C):
+    clusters, units = synth.gen_fuzz(11, W=W, C=C)
+    fwk = F.Framework(F.default_enabled_plugins())
+    snap = pack.Snapshot(clusters)
+    pols = synth.gen_override_policies(11, clusters) + R.special_policies(clusters)[0]
+    rng = np.random.default_rng([11, W])
+    op = np.stack([rng.integers(-1, len(pols), W), rng.integers(-1, len(pols), W)], 1).astype(np.int32)
+    return clusters, fwk, snap, pack.Batch(snap, fwk, units), pols, op
+
+
+def _match_results(c, case):
+    """kad_override_match on the last schedule's placements, checked against the checker on the same placements
+    written out (unit i's output slots, or its CurrentClusters entries when sticky); returns what it gave."""
+    clusters, fwk, snap, batch, pols, op = case
+    upload(c, snap, pols)
+    res = c.run(fwk, batch)
+    W, n_out = len(op), batch.n_out_slots
+    rw = OV.PolicySet(snap, pols).rule_words(op)
+    got_status, got_rows = c.override_match(op, None, rule_words=rw)
+    cur_off, cur_id = batch.arrays[pack.B_CUR_OFF], batch.arrays[pack.B_CUR_ID]
+    slots = []
+    for i in range(W):
+        if res.status[i] == pack.ST_OK:
+            slots.append(list(range(int(batch.out_off[i]), int(batch.out_off[i]) + int(res.count[i]))))
+        elif res.status[i] == pack.ST_STICKY:
+            slots.append(list(range(n_out + int(cur_off[i]), n_out + int(cur_off[i + 1]))))
+        else:
+            slots.append([])
+    cluster_of = np.concatenate([res.cluster[:n_out], cur_id]).astype(np.int32)
+    off = np.zeros(W + 1, np.int32)
+    off[1:] = np.cumsum([len(x) for x in slots])
+    flat = np.array([x for ss in slots for x in ss], np.int64)
+    want_status, want_rows = R.expected_match(pols, op, off, cluster_of[flat].astype(np.int32), clusters, rw)
+    assert (got_status == want_status).all()
+    assert (got_rows[flat] == want_rows).all()
+    rest = np.ones(len(got_rows), bool)
+    rest[flat] = False
+    assert not got_rows[rest].any()
+    _timing_ok(c.override_timing())
+    return got_status, got_rows
+
+
+def test_staging_buffer_from_results_small_large_small(ctx):
+    """One context, the placements of the last schedule: 3 units on C = 3, 300 units on C = 40, the 3 again —
+    each equal to the checker, the third equal to the first bit for bit."""
+    tiny, big = _results_case(3, 3), _results_case(300, 40)
+    first = _match_results(ctx, tiny)
+    _match_results(ctx, big)
+    again = _match_results(ctx, tiny)
+    assert again[0].tobytes() == first[0].tobytes() and again[1].tobytes() == first[1].tobytes()
+
+
 def test_snapshot_update_moves_a_label(ctx):
     clusters, snap0, pols, op, off, ids, rw, status, rows = inputs(3, 65)
     snap = pack.Snapshot(clusters)  # (the cached one stays as packed)

@@ -107,6 +107,41 @@ def _gpu_plan(ctx, rsp, replicas, clusters, existing, est, avoid, keep):
             {n: v for (n, _), v in zip(prefs, over) if v is not None})
 
 
+def test_select_rows_empty_inputs_and_null_offsets(ctx):
+    """kad_select_rows on its per-call staging buffer: no rows, an empty row beside a row of 3, and a null
+    row_off (KAD_EINVAL, no crash)."""
+    import ctypes
+    from kubeadmiral_amd import runtime
+    assert ctx.select_rows([], []) == []
+    (st0, sel0), (st1, sel1) = ctx.select_rows([[], [5, 9, 7]], [0, 2])
+    assert sel0 == [] and st1 == pack.ST_OK and sorted(sel1) == [1, 2]
+    z = np.zeros(4, np.int64)
+    o = np.zeros(4, np.int32)
+    P = ctypes.c_void_p
+    rc = ctx.L.kad_select_rows(ctx.h, 1, None, z.ctypes.data_as(P), z.ctypes.data_as(P), 0, o.ctypes.data_as(P),
+                               o.ctypes.data_as(P), o.ctypes.data_as(P))
+    assert rc == runtime.KAD_EINVAL
+    assert ctx.select_rows([[5, 9, 7]], [1]) == [(pack.ST_OK, [1])]  # the context still works
+
+
+def test_plan_rows_empty_inputs_and_null_offsets(ctx):
+    """kad_plan_rows on its per-call staging buffer: no rows, an empty row beside a row of 3 (equal weights, 6
+    replicas: 2 each, no overflow), and a null row_off (KAD_EINVAL, no crash)."""
+    import ctypes
+    from kubeadmiral_amd import runtime
+    assert ctx.plan_rows([]) == []
+    elems = [{"hash": 11 + i, "weight": 1, "min": 0, "max": None, "cap": None, "current": 0} for i in range(3)]
+    row = {"elems": elems, "total": 6, "avoid": False, "keep": False}
+    (p0, o0), (p1, o1) = ctx.plan_rows([{"elems": [], "total": 0, "avoid": False, "keep": False}, row])
+    assert p0 == [] and o0 == [] and p1 == [2, 2, 2]
+    z = np.zeros(4, np.int64)
+    P = ctypes.c_void_p
+    a = [z.ctypes.data_as(P)] * 12
+    rc = ctx.L.kad_plan_rows(ctx.h, 1, None, *a)
+    assert rc == runtime.KAD_EINVAL
+    assert ctx.plan_rows([row])[0][0] == [2, 2, 2]
+
+
 @pytest.mark.parametrize("path", ["lanes", "ws", "pairs"])
 @pytest.mark.parametrize("c", PLANNER, ids=[f"{case_id(c)}-a{int(c['avoidDisruption'])}k{int(c['keepUnschedulableReplicas'])}"
                                             for c in PLANNER])

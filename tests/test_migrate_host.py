@@ -263,6 +263,8 @@ def test_migrate_check_rejects():
     assert _check(arr, seg_cluster=at(0, MC.N_IDS)) == runtime.KAD_EINVAL
     assert _check(arr, seg_cluster=at(0, -1)) == runtime.KAD_EINVAL
     assert _check(arr, old_cluster=at(0, MC.N_IDS)) == runtime.KAD_EINVAL
+    assert _check(arr, old_cluster=at(0, -1)) == runtime.KAD_EINVAL
+    assert _check(arr, old_off=at(0, 1)) == runtime.KAD_EINVAL          # old_off not from 0 (its twin: arr itself)
     # descending or duplicate clusters within an object (the last object has four ascending segments)
     so = arr["obj_seg_off"]
     o = max(i for i in range(len(so) - 1) if so[i + 1] - so[i] >= 2)

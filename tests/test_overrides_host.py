@@ -269,6 +269,10 @@ def test_validator_rejects_out_of_range_ids():
            set_word(OV.O_REQ, 1, 1 << 20),                                                            # label key
            set_word(OV.O_POL_RULE_OFF, 1, -5), set_word(OV.O_RULE_PROG_OFF, 1, 1 << 28),
            set_word(OV.O_RULE_FLAGS, 0, 1 << 9), set_word(OV.O_POL_RULE_OFF, pset.P, pset.R + 1)]
+    # the two offset arrays the list above leaves out: a decrease, and a start other than 0 (the twin of each is
+    # the packed set itself, test_validator_accepts_packed_set)
+    for a in (OV.O_RULE_NAME_OFF, OV.O_REQ_OFF):
+        bad += [set_word(a, 1, -1), set_word(a, 0, 1)]
     for f in bad:
         assert _check(_patched(pset.blob, f), snap) == -1
 

@@ -84,3 +84,29 @@ def test_gpu_result_diff_equals_oracle(seed):
         assert (got & RD.OVERRIDES).any() and (got & RD.PLACEMENT).any()
     finally:
         ctx.close()
+
+
+@pytest.mark.gpu
+def test_gpu_result_diff_small_large_small():
+    """One context: 3 units on C = 3, 300 units on C = 30, the 3 again: the staging buffer grows, is reused and
+    is not reallocated on the way down. Each step equals the oracle, the third equals the first bit for bit."""
+    from kubeadmiral_amd import build, runtime
+    build.build()
+    ctx = runtime.Context(0)
+
+    def run(case):
+        snap, batch, fwk, units, objs = case
+        ctx.upload_snapshot(snap)
+        res = ctx.run(fwk, batch)
+        state = O.result_states(FTC, objs, snap.names)
+        got = ctx.result_diff(state)
+        want = RD.diff_flags(res, batch.out_off, state)
+        assert np.array_equal(got, want), np.nonzero(got != want)[0][:10]
+        return got
+    try:
+        tiny, big = _case(7, W=3, C=3), _case(8, W=300, C=30)
+        first = run(tiny)
+        run(big)
+        assert run(tiny).tobytes() == first.tobytes()
+    finally:
+        ctx.close()
