@@ -1,6 +1,7 @@
 """Build libkad.so (HIP, gfx950) in-tree, next to this file.
 
     python -m kubeadmiral_amd.build [--force] [--verbose]
+    python -m kubeadmiral_amd.build --digests [-DKAD_TUNING ...]   # .text / .rodata hashes per HIP source
 
 hipcc cross-compiles for gfx950 without a GPU. ``-ffp-contract=off`` keeps
 BalancedAllocation's and rsp's float64 arithmetic bit-identical to Go (no FMA
@@ -17,7 +18,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libkad.so")
 SOURCES = ["kad_kernels.hip", "kad_trigger.hip", "kad_delta.hip", "kad_diff.hip", "kad_explain.hip", "kad_override.hip", "kad_follower.hip", "kad_migrate.hip", "kad_api.hip", "kad_pack.cpp", "kad_objects.cpp"]
-HEADERS = ["kad_device.h", "kad_layout.h", "kad_route.h", "kad_wave.h", "kad_affinity.h", "kad_select.h", "kad_plan.h", "kad_pool.h", "kad_follower.h", "kad_migrate.h", "kad_ctx.h", "kad_arena.h"]
+HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h"))  # every header: none can be left out of the stamp
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("KAD_OFFLOAD_ARCH", "gfx950")
 
@@ -150,7 +151,23 @@ def _write_stamp(h: str) -> None:
     os.replace(STAMP + ".tmp", STAMP)
 
 
+def digests(extra=()) -> None:
+    """One line per HIP source: the .text and .rodata hashes of its gfx950 code object in the objects of this
+    flag set (stale ones compiled first, and linked beside them, never over libkad.so)."""
+    from . import isa_check
+
+    odir = _obj_dir(list(extra))
+    build(extra=extra, out=os.path.join(odir, "libkad.so"))
+    for src in SOURCES:
+        if src.endswith(".hip"):
+            d = isa_check.code_object_digests(os.path.join(odir, src + ".o"))
+            print(src, *(f"{k}={v}" for k, v in sorted(d.items())))
+
+
 if __name__ == "__main__":
+    if "--digests" in sys.argv:  # python -m kubeadmiral_amd.build --digests [-DKAD_TUNING ...]
+        digests([a for a in sys.argv[1:] if a.startswith("-D")])
+        sys.exit(0)
     build(force="--force" in sys.argv, verbose=True,
           extra=["-Rpass-analysis=kernel-resource-usage"] if "--resource-usage" in sys.argv else [])
     print(LIB)

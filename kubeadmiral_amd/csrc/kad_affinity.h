@@ -1,4 +1,4 @@
-// Device helpers shared by the schedule kernels (kad_kernels.hip) and the filter diagnosis
+// Device helpers shared by the schedule kernels (kad_k_full.h, kad_k_lean.h) and the filter diagnosis
 // (kad_explain.hip): a unit's predicate program in VGPR lanes and ClusterAffinity's filter over the
 // requirement bitmask rows.
 #pragma once

@@ -23,7 +23,7 @@ constexpr int WQ_HEADS = 64, WQ_STRIDE = 32;
 #define KAD_FIT_FENCES 256
 #endif
 constexpr int FIT_FENCES = KAD_FIT_FENCES;  // prep's LDS copy of every (fit_mp / FIT_FENCES)-th fit value
-constexpr int REQ_SEG_G = 8;  // chunks per req_mask_kernel wave (kad_kernels.hip REQ_G)
+constexpr int REQ_SEG_G = 8;  // chunks per req_mask_kernel wave (kad_k_rows.h REQ_G)
 // SnapDev::vrows: label value ids below VR_SLOTS get a cluster row; requirements naming at most
 // VR_MAX_VALS such values are ORs of rows (req_row_kernel)
 constexpr int VR_SLOTS = 64, VR_MAX_VALS = 5;

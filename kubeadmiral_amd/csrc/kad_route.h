@@ -21,7 +21,7 @@ struct RouteIn {
 static_assert(sizeof(RouteIn) == 4 * KAD_ROUTE_IN_FIELDS, "RouteIn is a flat int32 record");
 
 // Every kernel instantiation a schedule launch can name, with its kernel (read by kad_kernels.hip's table
-// alone). Families are contiguous: full, row, wide, lean.
+// alone). Families are contiguous: full, row, wide, lean (kad_k_full.h, kad_k_row.h, kad_k_wide.h, kad_k_lean.h).
 #define KAD_VARIANTS(X)                                                   \
   X(FULL_LDS, schedule_kernel<false>)                                     \
   X(FULL_GSCR, schedule_kernel<true>)                                     \

@@ -82,6 +82,24 @@ def device_code(obj: str):
     return dis, {m.group(1) for m in re.finditer(r"\s(\S+)\.kd$", syms, re.M)}
 
 
+def code_object_digests(obj: str) -> Dict[str, str]:
+    """SHA-256 of the raw ``.text`` and ``.rodata`` of the object's gfx950 code object ({} without device code).
+    The check of a pure move: both are equal before and after, where the whole ELF is not (the bundle carries
+    an id derived from the source's path, and the symbol and note sections may be laid out differently)."""
+    import hashlib
+
+    out = {}
+    with tempfile.TemporaryDirectory() as d:
+        co = _device_object(obj, d)
+        for sec in (".text", ".rodata") if co else ():
+            raw = os.path.join(d, sec[1:] + ".bin")  # (not written for a section the code object lacks)
+            _run([os.path.join(LLVM_BIN, "llvm-objcopy"), "-O", "binary", f"--only-section={sec}", co, raw])
+            if os.path.exists(raw):
+                with open(raw, "rb") as f:
+                    out[sec] = hashlib.sha256(f.read()).hexdigest()
+    return out
+
+
 def scan(disasm: str, kernels: set) -> List[str]:
     """Findings "function: line" for non-kernel functions loading through a register pair they zeroed."""
     funcs: Dict[str, List[str]] = {}

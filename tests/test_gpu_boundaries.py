@@ -186,10 +186,10 @@ def test_exact_feasible_list_lengths(ctx, case, C):
     512, 513, C-1, C}, as the first n, the last n and n strided clusters; MaxClusters None, 1, n - 1.
 
     The routing rules, read from the code: on the wide path (C = 1000) prep_kernel routes a unit to
-    schedule_row_kernel when its static words hold cnt > WIDE_P = 512 clusters (kad_kernels.hip prep_kernel
-    `cnt > WIDE_P`; without early routing the wide kernel does the same in wide_row_or_defer). On
+    schedule_row_kernel when its static words hold cnt > WIDE_P = 512 clusters (kad_k_prep.h prep_kernel
+    `cnt > WIDE_P`; without early routing the wide kernel does the same in unit_row_or_defer). On
     schedule_lean_kernel<0> (C = 1100) the rule is `NCH == 0 && n > P` with P = 64 * lean_qmax(0) = 64 *
-    LEAN_QMAX_DYN = 256: a list of 257 or more goes to lean_row_or_defer, the row list when
+    LEAN_QMAX_DYN = 256: a list of 257 or more goes to unit_row_or_defer, the row list when
     BatchDev::use_rows (clean, fold, fitfold, C <= ROW_MAX_C: asserted). 256 resp. 512 clusters stay in
     registers."""
     snap, batch, fwk, want, meta = case

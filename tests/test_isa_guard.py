@@ -60,6 +60,27 @@ def test_scan_tracks_redefinitions():
     assert len(found) == 1 and "s[8:9]" in found[0], found
 
 
+KERNEL = "__global__ void k(int* p, int n) { if ((int)threadIdx.x < n) p[threadIdx.x] = p[threadIdx.x] * %d + n; }\n"
+
+
+@pytest.mark.skipif(not _have_toolchain(), reason="hipcc / llvm tools absent")
+def test_code_object_digests_see_code_not_its_place(tmp_path):
+    """The check of a pure move (build --digests): a kernel moved into an included header, shifted by blank
+    lines and comments, hashes as the inline one; a changed constant does not."""
+    def digests(name, text):
+        src, obj = tmp_path / (name + ".hip"), tmp_path / (name + ".o")
+        src.write_text(text)
+        subprocess.run([HIPCC, f"--offload-arch={build.ARCH}", "-O3", "-c", str(src), "-o", str(obj)], check=True,
+                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+        return isa_check.code_object_digests(str(obj))
+
+    inline = digests("k", "#include <hip/hip_runtime.h>\n" + KERNEL % 3)
+    (tmp_path / "k_body.h").write_text("#pragma once\n\n// the kernel, in a header of its own\n\n\n" + KERNEL % 3)
+    moved = digests("k_moved", '#include <hip/hip_runtime.h>\n\n// moved out\n#include "k_body.h"\n')
+    assert set(inline) == {".text", ".rodata"} and moved == inline
+    assert digests("k_edited", "#include <hip/hip_runtime.h>\n" + KERNEL % 5)[".text"] != inline[".text"]
+
+
 @pytest.mark.skipif(not _have_toolchain(), reason="hipcc / llvm tools absent")
 def test_product_objects_are_clean():
     build.build()
