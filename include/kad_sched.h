@@ -777,6 +777,86 @@ int kad_migrate_route_eval(int32_t n_segments, int64_t n_pods, int32_t n_long, i
 int kad_migrate_last_route(kad_ctx* ctx, int32_t* out);
 int kad_migrate_debug_route(kad_ctx* ctx, int32_t force_width, int32_t force_long_min);
 
+/* ------------------------------------------------------ cluster status
+ * The producer of a FederatedCluster's status.resources is the federated-cluster controller
+ * (pkg/controllers/federatedcluster/clusterstatus.go:162-202, util.go:113-214): every collection interval and per
+ * ready member cluster, Allocatable = the per-name sum of status.allocatable over the schedulable nodes, Available
+ * = Allocatable minus the requests of every pod whose phase is not Succeeded or Failed, schedulableNodes = the
+ * count. kad_cluster_resources does that for a batch of member clusters.
+ *
+ * Quantities are int64 at one decimal scale per resource name, which the caller chooses (the device never
+ * sees it). n_res resource names R, 1 <= R <= 64; the caller leaves the name "pods" out of the node entries
+ * (util.go:192), after which pod entries naming it are ignored by the presence rule.
+ * Nodes: cl_node_off[K + 1] are a cluster's nodes; node_flags[N]: KAD_CS_NODE_SCHEDULABLE where isNodeSchedulable
+ * (util.go:114-132) holds; node_ent_off[N + 1] a node's entries (nent_res[EN] < R, nent_val[EN]), one per name
+ * of its status.allocatable.
+ * Pods: cl_pod_off[K + 1]; pod_flags[P]: KAD_CS_POD_TERMINAL for phase Succeeded / Failed; pod_ent_off[P + 1] a
+ * pod's entries (pent_res[EP] < R, pent_kind[EP]: 0 a container's request, 1 an init container's, 2 the
+ * overhead's; pent_val[EP]), ascending by (res, kind) within the pod, several of one (res, kind) allowed. The
+ * pod's request for a name is max(sum of kind 0, every kind 1) + sum of kind 2 (getPodResourceRequests,
+ * util.go:155-173, under values >= 0).
+ * Domain: every value >= 0; max nent_val x the most node entries of one cluster <= 2^62, and the same for pod
+ * entries: no sum can wrap. Anything else is KAD_EINVAL (the caller computes such clusters on the host).
+ *
+ * Outputs, cluster-major: alloc[K * R], avail[K * R] (may be negative), has[K] (bit r: some schedulable node of
+ * the cluster lists name r, even with value 0; where it is clear alloc and avail are 0 and requests for r are
+ * ignored), sched_nodes[K].
+ *
+ * Every offset array, resource id, kind, order rule, flag and the domain is validated on the host before
+ * anything is launched (KAD_EINVAL). Runs on the ctx stream (cstat_node_kernel, cstat_pod_kernel,
+ * cstat_combine_kernel: kad_cstat.hip); blocks until the outputs are in the caller's buffers. Needs no snapshot
+ * and reads no resident state, so a kad_group member accepts it. Leaves the last results, the timings and any
+ * later kad_schedule as they were. n_clusters == 0 returns 0 without launching. */
+#define KAD_CS_NODE_SCHEDULABLE 1u
+#define KAD_CS_POD_TERMINAL 1u
+#define KAD_CS_VALUE_BOUND (1ll << 62)
+typedef struct kad_cstat_batch {
+  int32_t n_clusters;  /* K */
+  int32_t n_res;       /* R */
+  int64_t n_nodes;     /* N */
+  int64_t n_pods;      /* P */
+  int64_t n_node_ents; /* EN */
+  int64_t n_pod_ents;  /* EP */
+  const int64_t* cl_node_off;  /* [K + 1] */
+  const uint8_t* node_flags;   /* [N] KAD_CS_NODE_* */
+  const int64_t* node_ent_off; /* [N + 1] */
+  const uint8_t* nent_res;     /* [EN] */
+  const int64_t* nent_val;     /* [EN] */
+  const int64_t* cl_pod_off;   /* [K + 1] */
+  const uint8_t* pod_flags;    /* [P] KAD_CS_POD_* */
+  const int64_t* pod_ent_off;  /* [P + 1] */
+  const uint8_t* pent_res;     /* [EP] */
+  const uint8_t* pent_kind;    /* [EP] 0 container, 1 init container, 2 overhead */
+  const int64_t* pent_val;     /* [EP] */
+} kad_cstat_batch;
+typedef struct kad_cstat_view {
+  int64_t* alloc;       /* [K * R] */
+  int64_t* avail;       /* [K * R] */
+  uint64_t* has;        /* [K] */
+  int64_t* sched_nodes; /* [K] */
+} kad_cstat_view;
+int kad_cluster_resources(kad_ctx* ctx, const kad_cstat_batch* batch, const kad_cstat_view* out);
+/* Host only (no device, no ctx): the same validation. */
+int kad_cstat_check(const kad_cstat_batch* batch, const kad_cstat_view* out);
+/* Device time of the last kad_cluster_resources that launched, from HIP events: ms[0] = cstat_node_kernel,
+ * ms[1] = cstat_pod_kernel + cstat_combine_kernel. No reference counterpart. */
+int kad_cstat_timing(kad_ctx* ctx, float ms[2]);
+/* What a kad_cluster_resources launches, as the library's one decision computes it (csrc/kad_cstat.h
+ * route_cstat; no device work, no ctx) for n_clusters clusters, n_long of them with more entries (node + pod)
+ * than the route's long_min, the others holding short_nodes nodes and short_pods pods, and n_chunks blocks of
+ * the long clusters' pods: out[KAD_CS_ROUTE_FIELDS] is [0] / [1] the lanes per cluster of the node / pod pass's
+ * group path (a power of two in [8, 64] from the mean nodes / pods per short cluster / 8), [2] long_min, [3]
+ * block threads, [4] / [5] blocks of the node / pod pass's group path, [6] blocks of the node pass's long path
+ * (one per long cluster), [7] blocks of the pod pass's long path (one per chunk). kad_cstat_last_route: the same
+ * record for the last kad_cluster_resources that launched (KAD_ESTATE before one). force_width /
+ * force_long_min of kad_cstat_debug_route (0: the route's own) replace [0], [1] and [2] for the following calls
+ * on this ctx. Measurement / tests only. */
+#define KAD_CS_ROUTE_FIELDS 8
+int kad_cstat_route_eval(int32_t n_clusters, int32_t n_long, int64_t short_nodes, int64_t short_pods, int32_t n_chunks,
+                         int32_t n_cu, int32_t* out);
+int kad_cstat_last_route(kad_ctx* ctx, int32_t* out);
+int kad_cstat_debug_route(kad_ctx* ctx, int32_t force_width, int32_t force_long_min);
+
 /* ------------------------------------------------ result application (§8 f3)
  * applySchedulingResult (pkg/controllers/scheduler/scheduler.go:632-695) writes a unit's result into its
  * federated object: the scheduler controller's placement (util.SetPlacementClusterNames,

@@ -421,6 +421,30 @@ class BatchReconciler:
                 out[i] = (batch.result(r, k), batch.capacities(r, k), updated[k])
         return out
 
+    # ------------------------------------------------------------------ cluster status
+    def reconcile_cluster_status(self, clusters: List[T.FederatedCluster], cluster_nodes: Sequence[Sequence[dict]],
+                                 cluster_pods: Sequence[Sequence[dict]], objs: Optional[Sequence[dict]] = None
+                                 ) -> List[str]:
+        """The federated-cluster controller's resource collection for a batch of member clusters
+        (pkg/controllers/federatedcluster/clusterstatus.go:162-202): ``cluster_nodes[i]`` / ``cluster_pods[i]``
+        are the node and pod dicts listed from ``clusters[i]``. One kad_cluster_resources sums them (clusters
+        outside the device's number domain on the host, clusterstatus.ClusterStatusBatch), the clusters whose
+        resources changed in value are replaced in ``clusters`` (in place) by copies with the new ``allocatable``
+        / ``available``, ``objs[i]`` (FederatedCluster dicts, optional) get ``status.resources``, and the resident
+        snapshot follows: a kad_snapshot_update of the changed columns, a repack where the delta cannot express
+        the change, nothing when no cluster changed. Returns the names of the changed clusters."""
+        from . import clusterstatus as CS
+
+        batch = CS.ClusterStatusBatch()
+        for nodes, pods in zip(cluster_nodes, cluster_pods):
+            batch.add(nodes, pods)
+        arrays = batch.arrays()
+        r = self.ctx.cluster_resources(**arrays) if batch.device else None
+        new, changed = batch.apply(r, clusters, objs)
+        clusters[:] = new
+        self.scheduler.set_clusters(clusters)
+        return changed
+
     # ------------------------------------------------------------------ the reconcile over JSON texts
     def reconcile_texts(self, texts: Sequence, policies: Sequence, clusters: List[T.FederatedCluster],
                         profiles: Optional[Dict[str, Optional[dict]]] = None

@@ -92,6 +92,20 @@ class MigrateView(ctypes.Structure):  # kad_migrate_view
                 ("backoff", ctypes.c_void_p)]
 
 
+class CstatBatch(ctypes.Structure):  # kad_cstat_batch
+    _fields_ = [("n_clusters", ctypes.c_int32), ("n_res", ctypes.c_int32), ("n_nodes", ctypes.c_int64),
+                ("n_pods", ctypes.c_int64), ("n_node_ents", ctypes.c_int64), ("n_pod_ents", ctypes.c_int64),
+                ("cl_node_off", ctypes.c_void_p), ("node_flags", ctypes.c_void_p), ("node_ent_off", ctypes.c_void_p),
+                ("nent_res", ctypes.c_void_p), ("nent_val", ctypes.c_void_p), ("cl_pod_off", ctypes.c_void_p),
+                ("pod_flags", ctypes.c_void_p), ("pod_ent_off", ctypes.c_void_p), ("pent_res", ctypes.c_void_p),
+                ("pent_kind", ctypes.c_void_p), ("pent_val", ctypes.c_void_p)]
+
+
+class CstatView(ctypes.Structure):  # kad_cstat_view
+    _fields_ = [("alloc", ctypes.c_void_p), ("avail", ctypes.c_void_p), ("has", ctypes.c_void_p),
+                ("sched_nodes", ctypes.c_void_p)]
+
+
 _lib = None
 
 
@@ -201,6 +215,14 @@ def load_library(path: str = LIB_PATH):
                                              ctypes.c_int32, P]
         L.kad_migrate_last_route.argtypes = [P, P]
         L.kad_migrate_debug_route.argtypes = [P, ctypes.c_int32, ctypes.c_int32]
+    if hasattr(L, "kad_cluster_resources"):
+        L.kad_cluster_resources.argtypes = [P, P, P]
+        L.kad_cstat_check.argtypes = [P, P]
+        L.kad_cstat_timing.argtypes = [P, P]
+        L.kad_cstat_route_eval.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64,
+                                           ctypes.c_int32, ctypes.c_int32, P]
+        L.kad_cstat_last_route.argtypes = [P, P]
+        L.kad_cstat_debug_route.argtypes = [P, ctypes.c_int32, ctypes.c_int32]
     L.kad_debug_inject_fault.argtypes = [P, I]
     L.kad_debug_plan_force_workspace.argtypes = [P, I]
     L.kad_trigger_suffix_upload.argtypes = [P, P, SZ]
@@ -366,6 +388,46 @@ def migrate_check(n_clusters: int, n_ids: int, now_ns: int, **arrays) -> int:
     snapshot of ``n_clusters`` clusters; no GPU. Returns the code."""
     b, v, _keepalive, _ = migrate_args(n_ids, now_ns, **arrays)
     return load_library().kad_migrate_check(ctypes.byref(b), ctypes.byref(v), n_clusters)
+
+
+CSTAT_ROUTE = ("node_width", "pod_width", "long_min", "threads", "node_grid", "pod_grid", "long_grid", "chunk_grid")
+
+
+def cstat_route_eval(n_clusters: int, n_long: int, short_nodes: int, short_pods: int, n_chunks: int,
+                     n_cu: int = 256) -> dict:
+    """kad_cstat_route_eval: the launch decision of a cluster_resources (needs no GPU)."""
+    out = (ctypes.c_int32 * len(CSTAT_ROUTE))()
+    rc = load_library().kad_cstat_route_eval(n_clusters, n_long, short_nodes, short_pods, n_chunks, n_cu, out)
+    if rc != 0:
+        raise ValueError(f"kad_cstat_route_eval: {rc}")
+    return dict(zip(CSTAT_ROUTE, out))
+
+
+_CSTAT_IN = (("cl_node_off", np.int64), ("node_flags", np.uint8), ("node_ent_off", np.int64), ("nent_res", np.uint8),
+             ("nent_val", np.int64), ("cl_pod_off", np.int64), ("pod_flags", np.uint8), ("pod_ent_off", np.int64),
+             ("pent_res", np.uint8), ("pent_kind", np.uint8), ("pent_val", np.int64))
+_CSTAT_OUT = (("alloc", np.int64, "KR"), ("avail", np.int64, "KR"), ("has", np.uint64, "K"), ("sched_nodes", np.int64, "K"))
+
+
+def cstat_args(n_res: int, **arrays):
+    """The kad_cstat_batch / kad_cstat_view of one call with the arrays that back them (the batch's fields by
+    name; the counts are taken from the arrays as they are, so that a malformed batch reaches the library's
+    validation). Returns (batch, view, the input arrays, the output arrays by name)."""
+    a = {k: np.ascontiguousarray(arrays[k], dt).reshape(-1) for k, dt in _CSTAT_IN}
+    K = max(0, len(a["cl_node_off"]) - 1)
+    n = {"K": K, "KR": K * max(0, int(n_res))}
+    out = {k: np.zeros(max(1, n[dim]), dt) for k, dt, dim in _CSTAT_OUT}
+    b = CstatBatch(K, int(n_res), len(a["node_flags"]), len(a["pod_flags"]), len(a["nent_val"]), len(a["pent_val"]),
+                   *(a[k].ctypes.data if len(a[k]) else None for k, _ in _CSTAT_IN))
+    v = CstatView(*(out[k].ctypes.data for k, _, _ in _CSTAT_OUT))
+    return b, v, a, {k: out[k][:n[dim]] for k, _, dim in _CSTAT_OUT}
+
+
+def cstat_check(n_res: int, **arrays) -> int:
+    """kad_cstat_check: kad_cluster_resources' validation of :func:`cstat_args` arguments; no GPU. Returns the
+    code."""
+    b, v, _keepalive, _ = cstat_args(n_res, **arrays)
+    return load_library().kad_cstat_check(ctypes.byref(b), ctypes.byref(v))
 
 
 class Context:
@@ -668,6 +730,31 @@ class Context:
         """kad_migrate_debug_route: the group width / long_min of the following migrate_estimate() calls
         (0: the route's own). Measurement only."""
         self._chk(self.L.kad_migrate_debug_route(self.h, width, long_min))
+
+    def cluster_resources(self, n_res: int, **arrays) -> dict:
+        """kad_cluster_resources → {alloc[K * R], avail[K * R], has[K], sched_nodes[K]}. Arguments as
+        :func:`cstat_args` (clusterstatus.ClusterStatusBatch.arrays())."""
+        b, v, _keepalive, out = cstat_args(n_res, **arrays)
+        self._chk(self.L.kad_cluster_resources(self.h, ctypes.byref(b), ctypes.byref(v)))
+        return out
+
+    def cstat_timing(self):
+        """kad_cstat_timing: device ms of the last cluster_resources() — (cstat_node_kernel, cstat_pod_kernel +
+        cstat_combine_kernel)."""
+        ms = (ctypes.c_float * 2)()
+        self._chk(self.L.kad_cstat_timing(self.h, ms))
+        return float(ms[0]), float(ms[1])
+
+    def cstat_last_route(self) -> dict:
+        """kad_cstat_last_route: what the last cluster_resources() launched (cstat_route_eval's record)."""
+        out = (ctypes.c_int32 * len(CSTAT_ROUTE))()
+        self._chk(self.L.kad_cstat_last_route(self.h, out))
+        return dict(zip(CSTAT_ROUTE, out))
+
+    def cstat_debug_route(self, width: int = 0, long_min: int = 0) -> None:
+        """kad_cstat_debug_route: the group width / long_min of the following cluster_resources() calls (0: the
+        route's own). Measurement only."""
+        self._chk(self.L.kad_cstat_debug_route(self.h, width, long_min))
 
     def select_rows(self, rows: Sequence[Sequence[int]], max_clusters: Sequence[Optional[int]], flags: int = 0):
         """MaxCluster on explicit score rows → per row (status, sorted selected positions)."""

@@ -1216,3 +1216,111 @@ def migration_objects(a: dict, names, type_config=None):
         cobjs.append(co)
         pods.append(pl)
     return ftc, objs, cobjs, pods
+
+
+# ------------------------------------------------------------ cluster status (kad_cluster_resources)
+CSTAT_NAMES = ("cpu", "memory", "ephemeral-storage", "example.com/gpu")
+CSTAT_SCALES = (3, 0, 0, 0)  # cpu in milli, the others in units
+
+
+def gen_cluster_status(seed: int, K: int, nodes_median: float = 300.0, sigma: float = 1.3, pods_per_node: float = 30.0,
+                       max_nodes: int = 20000, schedulable: float = 0.95, terminal: float = 0.1):
+    """Seeded nodes and pods of ``K`` member clusters as kad_cluster_resources' arrays, sizes skewed: nodes per
+    cluster log-normal around ``nodes_median`` (``sigma``; clipped to [3, ``max_nodes``]: tens to thousands), pods
+    about ``pods_per_node`` times as many. Every node lists cpu, memory and ephemeral-storage, one in ten a GPU
+    resource; a share ``schedulable`` of the nodes is schedulable. A pod has 1-3 containers requesting cpu and
+    memory, one in ten an init container, one in twenty an overhead, one in fifty a GPU; a share ``terminal`` is
+    Succeeded / Failed. Returns (arrays — the keyword arguments of Context.cluster_resources —, CSTAT_NAMES,
+    CSTAT_SCALES)."""
+    rng = np.random.default_rng([seed, 0xC57A])
+    nn = np.clip(rng.lognormal(np.log(nodes_median), sigma, K), 3, max_nodes).astype(np.int64)
+    npod = np.maximum(0, (nn * pods_per_node * rng.uniform(0.6, 1.4, K)).astype(np.int64))
+    cn = np.zeros(K + 1, np.int64)
+    cn[1:] = np.cumsum(nn)
+    cp = np.zeros(K + 1, np.int64)
+    cp[1:] = np.cumsum(npod)
+    N, P = int(cn[-1]), int(cp[-1])
+    # nodes: entries ascend by resource id; slot 3 (the GPU) on one node in ten
+    gpu = rng.random(N) < 0.1
+    ncnt = np.stack([np.ones(N, np.int8)] * 3 + [gpu.astype(np.int8)], axis=1)
+    nent_res = np.repeat(np.tile(np.arange(4, dtype=np.uint8), N), ncnt.ravel())
+    ne = np.zeros(N + 1, np.int64)
+    ne[1:] = np.cumsum(ncnt.sum(axis=1, dtype=np.int64))
+    cores = rng.choice(np.array([4, 8, 16, 32, 64, 96, 128], np.int64), N)
+    per_node = np.stack([cores * 1000 - rng.integers(0, 500, N), cores * (4 << 30), rng.integers(100, 2000, N) << 30,
+                         np.full(N, 8, np.int64)], axis=1)
+    nent_val = per_node.ravel()[ncnt.ravel() > 0]
+    node_flags = np.where(rng.random(N) < schedulable, 1, 0).astype(np.uint8)
+    # pods: nine (resource, kind) slots in ascending order over cpu, memory and the GPU
+    ncont = rng.integers(1, 4, P).astype(np.int8)
+    init = (rng.random(P) < 0.1).astype(np.int8)
+    ovh = (rng.random(P) < 0.05).astype(np.int8)
+    pgpu = (rng.random(P) < 0.02).astype(np.int8)
+    zero = np.zeros(P, np.int8)
+    pcnt = np.stack([ncont, init, ovh, ncont, init, ovh, pgpu, zero, zero], axis=1)
+    slot = np.repeat(np.tile(np.arange(9, dtype=np.uint8), P), pcnt.ravel())
+    pe = np.zeros(P + 1, np.int64)
+    pe[1:] = np.cumsum(pcnt.sum(axis=1, dtype=np.int64))
+    pent_res = np.array([0, 0, 0, 1, 1, 1, 3, 3, 3], np.uint8)[slot]
+    pent_kind = (slot % 3).astype(np.uint8)
+    EP = len(slot)
+    pent_val = np.where(pent_res == 0, rng.integers(10, 500, EP),
+                        np.where(pent_res == 1, rng.integers(32, 2048, EP) << 20, 1)).astype(np.int64)
+    pod_flags = np.where(rng.random(P) < terminal, 1, 0).astype(np.uint8)
+    a = dict(n_res=4, cl_node_off=cn, node_flags=node_flags, node_ent_off=ne, nent_res=nent_res,
+             nent_val=nent_val.astype(np.int64), cl_pod_off=cp, pod_flags=pod_flags, pod_ent_off=pe, pent_res=pent_res,
+             pent_kind=pent_kind, pent_val=pent_val)
+    return a, CSTAT_NAMES, CSTAT_SCALES
+
+
+def cluster_status_objects(a: dict, names=CSTAT_NAMES, scales=CSTAT_SCALES):
+    """The batch of :func:`gen_cluster_status` as the controller sees it: per cluster the node dicts (allocatable
+    with a ``pods`` count; the unschedulable ones cordoned, tainted NoSchedule / NoExecute or not Ready in turn)
+    and the pod dicts (containers, init containers, overhead, phase). For small batches: tests. Returns
+    (cluster_nodes, cluster_pods)."""
+    suffix = {0: "", 3: "m", 6: "u", 9: "n"}
+
+    def text(r: int, v: int) -> str:
+        return f"{int(v)}{suffix[scales[r]]}"
+
+    cluster_nodes, cluster_pods = [], []
+    for k in range(len(a["cl_node_off"]) - 1):
+        nodes = []
+        for n in range(int(a["cl_node_off"][k]), int(a["cl_node_off"][k + 1])):
+            alloc = {"pods": "110"}
+            for e in range(int(a["node_ent_off"][n]), int(a["node_ent_off"][n + 1])):
+                alloc[names[int(a["nent_res"][e])]] = text(int(a["nent_res"][e]), a["nent_val"][e])
+            node = {"metadata": {"name": f"node-{k}-{n}"}, "spec": {},
+                    "status": {"allocatable": alloc, "conditions": [{"type": "Ready", "status": "True"}]}}
+            if not a["node_flags"][n] & 1:
+                how = n % 4
+                if how == 0:
+                    node["spec"]["unschedulable"] = True
+                elif how in (1, 2):
+                    node["spec"]["taints"] = [{"key": "maintenance", "effect": ("NoSchedule", "NoExecute")[how - 1]}]
+                else:
+                    node["status"]["conditions"] = [{"type": "Ready", "status": "Unknown"}]
+            elif n % 7 == 0:
+                node["spec"]["taints"] = [{"key": "spot", "effect": "PreferNoSchedule"}]
+            nodes.append(node)
+        pods = []
+        for p in range(int(a["cl_pod_off"][k]), int(a["cl_pod_off"][k + 1])):
+            by_kind = ({}, {}, {})  # kind → resource → the values in order
+            for e in range(int(a["pod_ent_off"][p]), int(a["pod_ent_off"][p + 1])):
+                by_kind[int(a["pent_kind"][e])].setdefault(int(a["pent_res"][e]), []).append(int(a["pent_val"][e]))
+
+            def containers(m):
+                return [{"name": f"c{j}", "resources": {"requests": {names[r]: text(r, v[j]) for r, v in m.items()
+                                                                     if j < len(v)}}}
+                        for j in range(max((len(v) for v in m.values()), default=0))]
+
+            spec = {"containers": containers(by_kind[0])}
+            if by_kind[1]:
+                spec["initContainers"] = containers(by_kind[1])
+            if by_kind[2]:
+                spec["overhead"] = {names[r]: text(r, sum(v)) for r, v in by_kind[2].items()}
+            phase = ("Succeeded", "Failed")[p % 2] if a["pod_flags"][p] & 1 else "Running"
+            pods.append({"metadata": {"name": f"pod-{k}-{p}"}, "spec": spec, "status": {"phase": phase}})
+        cluster_nodes.append(nodes)
+        cluster_pods.append(pods)
+    return cluster_nodes, cluster_pods
