@@ -857,6 +857,107 @@ int kad_cstat_route_eval(int32_t n_clusters, int32_t n_long, int64_t short_nodes
 int kad_cstat_last_route(kad_ctx* ctx, int32_t* out);
 int kad_cstat_debug_route(kad_ctx* ctx, int32_t force_width, int32_t force_long_min);
 
+/* ------------------------------------------------------ status aggregation
+ * The status aggregator (pkg/controllers/statusaggregator/controller.go:249-348) folds, per source object and on
+ * every member-object event, the statuses of the object's copies in the member clusters into the source
+ * object's status. kad_status_aggregate does the numeric part of its Deployment plugin (plugins/
+ * deployment.go:42-186) or its Job plugin (plugins/job.go:43-163) for a batch of source objects of one kind,
+ * and compares the result with each object's old status.
+ *
+ * kind: KAD_SAGG_DEPLOYMENT or KAD_SAGG_JOB. obj_seg_off[O + 1] are an object's segments, one per member cluster
+ * that holds a copy (the order within an object does not matter).
+ * Per object: obj_flags[O]: KAD_SAGG_OBJ_UPTODATE = clusterObjsUpToDate (propagationstatus.IsResourcePropagated);
+ * KAD_SAGG_OBJ_ERROR = the caller found an object-level error (a member's status missing, not a map or not
+ * convertible): every output of the object is 0, changed included, and its segments are not read;
+ * KAD_SAGG_OBJ_OLD_OTHER = the old status can never compare equal (another key, an explicit zero, a value that
+ * is not an integer): changed is 1. obj_generation[O] = metadata.generation and obj_observed[O] = the current
+ * status.observedGeneration (Deployment only; null for a Job). old_vals[NOLD][O], row-major, the old status with
+ * an absent key as 0: Deployment NOLD = 6: replicas, updatedReplicas, readyReplicas, availableReplicas,
+ * unavailableReplicas, observedGeneration; Job NOLD = 5: active, succeeded, failed, startTime (INT64_MAX: none),
+ * completionTime (INT64_MIN: none).
+ * Per segment: seg_vals[NV][S], row-major int32: Deployment NV = 5 (the five replica counts in the order above),
+ * Job NV = 3 (active, succeeded, failed). seg_flags[S]: KAD_SAGG_SEG_NIL = the member's status is nil (skipped;
+ * it clears the Deployment's observed-generation flag and still counts as a member of the Job);
+ * Deployment: KAD_SAGG_SEG_SYNCED = the cluster is listed in fedObject.status.clusters, with seg_synced[S] its
+ * generation there and seg_observed[S] the member's status.observedGeneration; Job: KAD_SAGG_SEG_START = startTime
+ * is set, seg_start[S]; KAD_SAGG_SEG_DONE = completionTime is set and not zero, seg_done[S]; KAD_SAGG_SEG_FAILED =
+ * not DONE and a Failed condition with status True. The arrays of the other kind may be null.
+ * Times are int64 Unix seconds. Domain: |t| <= KAD_SAGG_TIME_MAX and t != KAD_SAGG_TIME_ZERO (Go's zero time,
+ * which makes the reference's start-time rule depend on its map order: the caller answers such objects itself),
+ * checked where the segment's flag makes the time count.
+ *
+ * Outputs per object: sums[NV][O], row-major: the int32 sums, wrapped as Go's. Deployment: observed[O] =
+ * obj_generation if the object is UPTODATE, no member is NIL and every member is SYNCED with seg_synced ==
+ * seg_observed, else obj_observed. Job: start_min[O] (INT64_MAX: none), done_max[O] (INT64_MIN: none), n_done[O],
+ * n_failed[O], finished[O] = n_done + n_failed > 0 and equal to the object's segments (the aggregated condition
+ * is appended; the caller builds it and ORs its compare into changed; completionTime = done_max is written only
+ * if also n_failed == 0). changed[O]: the new numeric status differs from old_vals, or OLD_OTHER. The arrays of
+ * the other kind may be null.
+ *
+ * The kind, the offsets, every flag (unknown to the kind; NIL with START / DONE / FAILED; DONE with FAILED) and
+ * the time domain are validated on the host before anything is launched (KAD_EINVAL). Runs on the ctx stream
+ * (sagg_kernel: kad_statusagg.hip); blocks until the outputs are in the caller's buffers. Needs no snapshot and
+ * reads no resident state, so a kad_group member accepts it. Leaves the last results, the timings and any later
+ * kad_schedule as they were. n_objects == 0 returns 0 without launching. */
+#define KAD_SAGG_DEPLOYMENT 0
+#define KAD_SAGG_JOB 1
+#define KAD_SAGG_OBJ_UPTODATE 1u
+#define KAD_SAGG_OBJ_ERROR 2u
+#define KAD_SAGG_OBJ_OLD_OTHER 4u
+#define KAD_SAGG_SEG_NIL 1u
+#define KAD_SAGG_SEG_SYNCED 2u
+#define KAD_SAGG_SEG_START 4u
+#define KAD_SAGG_SEG_DONE 8u
+#define KAD_SAGG_SEG_FAILED 16u
+#define KAD_SAGG_TIME_MAX (1ll << 61)
+#define KAD_SAGG_TIME_ZERO (-62135596800ll) /* time.Time{} as Unix seconds */
+typedef struct kad_sagg_batch {
+  int32_t kind;       /* KAD_SAGG_DEPLOYMENT / KAD_SAGG_JOB */
+  int32_t n_objects;  /* O */
+  int32_t n_segments; /* S */
+  int32_t reserved;   /* 0 */
+  const int32_t* obj_seg_off;    /* [O + 1] */
+  const uint8_t* obj_flags;      /* [O] KAD_SAGG_OBJ_* */
+  const int64_t* obj_generation; /* [O] Deployment */
+  const int64_t* obj_observed;   /* [O] Deployment */
+  const int64_t* old_vals;       /* [NOLD * O] */
+  const int32_t* seg_vals;       /* [NV * S] */
+  const uint8_t* seg_flags;      /* [S] KAD_SAGG_SEG_* */
+  const int64_t* seg_observed;   /* [S] Deployment */
+  const int64_t* seg_synced;     /* [S] Deployment */
+  const int64_t* seg_start;      /* [S] Job */
+  const int64_t* seg_done;       /* [S] Job */
+} kad_sagg_batch;
+typedef struct kad_sagg_view {
+  int32_t* sums;      /* [NV * O] */
+  uint8_t* changed;   /* [O] */
+  int64_t* observed;  /* [O] Deployment */
+  int64_t* start_min; /* [O] Job */
+  int64_t* done_max;  /* [O] Job */
+  int32_t* n_done;    /* [O] Job */
+  int32_t* n_failed;  /* [O] Job */
+  uint8_t* finished;  /* [O] Job */
+} kad_sagg_view;
+int kad_status_aggregate(kad_ctx* ctx, const kad_sagg_batch* batch, const kad_sagg_view* out);
+/* Host only (no device, no ctx): the same validation. */
+int kad_sagg_check(const kad_sagg_batch* batch, const kad_sagg_view* out);
+/* Device time of the last kad_status_aggregate that launched, from HIP events: ms[0] = sagg_kernel. No reference
+ * counterpart. */
+int kad_sagg_timing(kad_ctx* ctx, float ms[1]);
+/* What a kad_status_aggregate launches, as the library's one decision computes it (csrc/kad_statusagg.h
+ * route_sagg; no device work, no ctx) for n_objects objects, n_long of them (not in error) with more segments
+ * than the route's long_min, the other objects that are not in error holding short_segments segments:
+ * out[KAD_SAGG_ROUTE_FIELDS] is [0] the lanes per object of the group path (a power of two in [1, 64] from the mean
+ * segments per short object / 8), [1] long_min, [2] block threads, [3] blocks of the group path, [4] blocks of the
+ * long path (one per long object), [5] objects between two consecutive objects of one lane group.
+ * kad_sagg_last_route: the same record for the last kad_status_aggregate that launched (KAD_ESTATE before one).
+ * force_width (a power of two in [1, 64]) / force_long_min of kad_sagg_debug_route (0: the route's own) replace
+ * [0] and [1] for the following calls on this ctx. Measurement / tests only. */
+#define KAD_SAGG_ROUTE_FIELDS 6
+int kad_sagg_route_eval(int32_t n_objects, int32_t n_long, int64_t short_segments, int32_t n_cu, int32_t* out);
+int kad_sagg_last_route(kad_ctx* ctx, int32_t* out);
+int kad_sagg_debug_route(kad_ctx* ctx, int32_t force_width, int32_t force_long_min);
+
 /* ------------------------------------------------ result application (§8 f3)
  * applySchedulingResult (pkg/controllers/scheduler/scheduler.go:632-695) writes a unit's result into its
  * federated object: the scheduler controller's placement (util.SetPlacementClusterNames,

@@ -37,6 +37,14 @@ STATUS_ERROR = "Error"    # worker.StatusError
 
 
 @dataclass
+class StatusAggOutcome:
+    """One source object's outcome of :meth:`BatchReconciler.reconcile_status_aggregation`."""
+    status: str              # STATUS_ALL_OK / STATUS_ERROR
+    need_update: bool        # the plugin's needUpdate: the source object was written and is to be updated
+    error: Optional[str]     # the reference's error return
+
+
+@dataclass
 class ReconcileOutcome:
     status: str                                  # STATUS_ALL_OK / STATUS_ERROR
     stage: str = ""                              # where the reconcile ended (see BatchReconciler.reconcile)
@@ -444,6 +452,45 @@ class BatchReconciler:
         clusters[:] = new
         self.scheduler.set_clusters(clusters)
         return changed
+
+    # ------------------------------------------------------------------ status aggregation
+    def reconcile_status_aggregation(self, sources: Sequence[dict], fed_objects: Sequence[Optional[dict]],
+                                     cluster_objs: Sequence[Dict[str, dict]], now: Optional[int] = None
+                                     ) -> List[StatusAggOutcome]:
+        """The status aggregator's reconcile for a batch of source objects
+        (pkg/controllers/statusaggregator/controller.go:249-348): ``sources[i]`` is a Deployment or a Job (by its
+        ``kind``), ``fed_objects[i]`` its federated object and ``cluster_objs[i]`` its copies in the ready member
+        clusters (cluster name → object). One kad_status_aggregate per kind folds the members' statuses
+        (statusagg.StatusAggBatch: objects outside the device's time domain on the host); the source objects
+        whose status or digests annotation changed are written in place, the others stay untouched. ``now``
+        (Unix seconds, default the clock) stamps the Jobs' aggregated conditions, once per call. A source or
+        federated object that is absent or being deleted is AllOK without an update (controller.go:270-284).
+        Fetching the member objects and the Update call stay with the caller."""
+        import time
+
+        from . import statusagg as SA
+
+        now = int(time.time()) if now is None else int(now)
+        out: List[Optional[StatusAggOutcome]] = [None] * len(sources)
+        batches = {SA.DEPLOYMENT: (SA.StatusAggBatch(SA.DEPLOYMENT), []), SA.JOB: (SA.StatusAggBatch(SA.JOB), [])}
+        for i, (src, fed, objs) in enumerate(zip(sources, fed_objects, cluster_objs)):
+            gone = lambda o: o is None or (o.get("metadata") or {}).get("deletionTimestamp") is not None  # noqa: E731
+            if gone(src) or gone(fed):
+                out[i] = StatusAggOutcome(STATUS_ALL_OK, False, None)
+                continue
+            kind = {"Deployment": SA.DEPLOYMENT, "Job": SA.JOB}.get(src.get("kind"))
+            if kind is None:
+                raise ValueError(f"reconcile_status_aggregation: no plugin for kind {src.get('kind')!r}")
+            batches[kind][0].add(src, fed, objs)
+            batches[kind][1].append(i)
+        for batch, index in batches.values():
+            if not index:
+                continue
+            arrays = batch.arrays()
+            r = self.ctx.status_aggregate(**arrays) if batch.device else None
+            for i, (need, err) in zip(index, batch.apply(r, now)):
+                out[i] = StatusAggOutcome(STATUS_ERROR if err else STATUS_ALL_OK, need, str(err) if err else None)
+        return out  # type: ignore[return-value]
 
     # ------------------------------------------------------------------ the reconcile over JSON texts
     def reconcile_texts(self, texts: Sequence, policies: Sequence, clusters: List[T.FederatedCluster],

@@ -1,7 +1,7 @@
 // The context behind the C ABI (include/kad_sched.h) and the host helpers every entry point shares: each
 // stage's host half (kad_api.hip, and kad_diff / kad_explain / kad_override / kad_follower / kad_migrate /
-// kad_cstat / kad_trigger.hip below their kernels) includes this. The first part needs no HIP (KAD_HOST_ONLY stops
-// there: tests/arena_main.cpp).
+// kad_cstat / kad_statusagg / kad_trigger.hip below their kernels) includes this. The first part needs no HIP
+// (KAD_HOST_ONLY stops there: tests/arena_main.cpp).
 #pragma once
 
 #include <atomic>
@@ -76,6 +76,7 @@ inline bool csr_bad(const O* off, const int32_t* data, int64_t n, int64_t lo, in
 #include "kad_follower.h"
 #include "kad_migrate.h"
 #include "kad_cstat.h"
+#include "kad_statusagg.h"
 
 // A device buffer that grows on demand (grow) and frees itself: a ctx member is released by kad_ctx_destroy's
 // delete, a per-call one at the end of its scope — no list of buffers to keep.
@@ -102,7 +103,8 @@ struct Stage {
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   bool ran = false;
 };
-enum StageId { STG_DIFF, STG_EXPLAIN, STG_OVERRIDE, STG_FOLLOWER, STG_MIGRATE, STG_TRIGGER, STG_CSTAT, STG_COUNT };
+enum StageId { STG_DIFF, STG_EXPLAIN, STG_OVERRIDE, STG_FOLLOWER, STG_MIGRATE, STG_TRIGGER, STG_CSTAT, STG_SAGG,
+               STG_COUNT };
 
 struct kad_ctx {
   int device = 0;
@@ -171,6 +173,8 @@ struct kad_ctx {
   int mig_force_width = 0, mig_force_long_min = 0;  // kad_migrate_debug_route (0: the route's own)
   kad::CstatRoute cs_route{};      // what the last kad_cluster_resources launched (kad_cstat_last_route)
   int cs_force_width = 0, cs_force_long_min = 0;    // kad_cstat_debug_route (0: the route's own)
+  kad::SaggRoute sagg_route{};     // what the last kad_status_aggregate launched (kad_sagg_last_route)
+  int sagg_force_width = 0, sagg_force_long_min = 0;  // kad_sagg_debug_route (0: the route's own)
   bool group_member = false;   // owned by a kad_group: its resident results are a shard's
   // HIP event records around the stages (kad_set_timing); timed = the last
   // kad_schedule recorded them

@@ -106,6 +106,20 @@ class CstatView(ctypes.Structure):  # kad_cstat_view
                 ("sched_nodes", ctypes.c_void_p)]
 
 
+class SaggBatch(ctypes.Structure):  # kad_sagg_batch
+    _fields_ = [("kind", ctypes.c_int32), ("n_objects", ctypes.c_int32), ("n_segments", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("obj_seg_off", ctypes.c_void_p), ("obj_flags", ctypes.c_void_p),
+                ("obj_generation", ctypes.c_void_p), ("obj_observed", ctypes.c_void_p), ("old_vals", ctypes.c_void_p),
+                ("seg_vals", ctypes.c_void_p), ("seg_flags", ctypes.c_void_p), ("seg_observed", ctypes.c_void_p),
+                ("seg_synced", ctypes.c_void_p), ("seg_start", ctypes.c_void_p), ("seg_done", ctypes.c_void_p)]
+
+
+class SaggView(ctypes.Structure):  # kad_sagg_view
+    _fields_ = [("sums", ctypes.c_void_p), ("changed", ctypes.c_void_p), ("observed", ctypes.c_void_p),
+                ("start_min", ctypes.c_void_p), ("done_max", ctypes.c_void_p), ("n_done", ctypes.c_void_p),
+                ("n_failed", ctypes.c_void_p), ("finished", ctypes.c_void_p)]
+
+
 _lib = None
 
 
@@ -223,6 +237,13 @@ def load_library(path: str = LIB_PATH):
                                            ctypes.c_int32, ctypes.c_int32, P]
         L.kad_cstat_last_route.argtypes = [P, P]
         L.kad_cstat_debug_route.argtypes = [P, ctypes.c_int32, ctypes.c_int32]
+    if hasattr(L, "kad_status_aggregate"):
+        L.kad_status_aggregate.argtypes = [P, P, P]
+        L.kad_sagg_check.argtypes = [P, P]
+        L.kad_sagg_timing.argtypes = [P, P]
+        L.kad_sagg_route_eval.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, P]
+        L.kad_sagg_last_route.argtypes = [P, P]
+        L.kad_sagg_debug_route.argtypes = [P, ctypes.c_int32, ctypes.c_int32]
     L.kad_debug_inject_fault.argtypes = [P, I]
     L.kad_debug_plan_force_workspace.argtypes = [P, I]
     L.kad_trigger_suffix_upload.argtypes = [P, P, SZ]
@@ -428,6 +449,51 @@ def cstat_check(n_res: int, **arrays) -> int:
     code."""
     b, v, _keepalive, _ = cstat_args(n_res, **arrays)
     return load_library().kad_cstat_check(ctypes.byref(b), ctypes.byref(v))
+
+
+SAGG_ROUTE = ("width", "long_min", "threads", "grid", "long_grid", "stride")
+SAGG_DEPLOYMENT, SAGG_JOB = 0, 1
+SAGG_NV = {SAGG_DEPLOYMENT: 5, SAGG_JOB: 3}    # int32 rows of seg_vals / sums
+SAGG_NOLD = {SAGG_DEPLOYMENT: 6, SAGG_JOB: 5}  # int64 rows of old_vals
+
+
+def sagg_route_eval(n_objects: int, n_long: int, short_segments: int, n_cu: int = 256) -> dict:
+    """kad_sagg_route_eval: the launch decision of a status_aggregate (needs no GPU)."""
+    out = (ctypes.c_int32 * len(SAGG_ROUTE))()
+    rc = load_library().kad_sagg_route_eval(n_objects, n_long, short_segments, n_cu, out)
+    if rc != 0:
+        raise ValueError(f"kad_sagg_route_eval: {rc}")
+    return dict(zip(SAGG_ROUTE, out))
+
+
+_SAGG_IN = (("obj_seg_off", np.int32, 2), ("obj_flags", np.uint8, 2), ("obj_generation", np.int64, 0),
+            ("obj_observed", np.int64, 0), ("old_vals", np.int64, 2), ("seg_vals", np.int32, 2), ("seg_flags", np.uint8, 2),
+            ("seg_observed", np.int64, 0), ("seg_synced", np.int64, 0), ("seg_start", np.int64, 1), ("seg_done", np.int64, 1))
+_SAGG_OUT = (("sums", np.int32, 2), ("changed", np.uint8, 2), ("observed", np.int64, 0), ("start_min", np.int64, 1),
+             ("done_max", np.int64, 1), ("n_done", np.int32, 1), ("n_failed", np.int32, 1), ("finished", np.uint8, 1))
+
+
+def sagg_args(kind: int, **arrays):
+    """The kad_sagg_batch / kad_sagg_view of one call with the arrays that back them (the batch's fields by name;
+    the counts are taken from the arrays as they are, so that a malformed batch reaches the library's
+    validation; the other kind's arrays are left null). Returns (batch, view, the input arrays, the output
+    arrays by name: ``sums`` as [NV, O])."""
+    mine = lambda which: which == 2 or which == (1 if kind == SAGG_JOB else 0)  # noqa: E731
+    a = {k: np.ascontiguousarray(arrays[k], dt).reshape(-1) for k, dt, which in _SAGG_IN if mine(which) and k in arrays}
+    O_, S_ = len(a["obj_flags"]), len(a["seg_flags"])
+    nv = SAGG_NV.get(kind, 5)
+    out = {k: np.zeros(max(1, O_ * (nv if k == "sums" else 1)), dt) for k, dt, which in _SAGG_OUT if mine(which)}
+    b = SaggBatch(int(kind), O_, S_, 0, *(a[k].ctypes.data if k in a and len(a[k]) else None for k, _, _ in _SAGG_IN))
+    v = SaggView(*(out[k].ctypes.data if k in out else None for k, _, _ in _SAGG_OUT))
+    res = {k: (o[:nv * O_].reshape(nv, O_) if k == "sums" else o[:O_]) for k, o in out.items()}
+    return b, v, a, res
+
+
+def sagg_check(kind: int, **arrays) -> int:
+    """kad_sagg_check: kad_status_aggregate's validation of :func:`sagg_args` arguments; no GPU. Returns the
+    code."""
+    b, v, _keepalive, _ = sagg_args(kind, **arrays)
+    return load_library().kad_sagg_check(ctypes.byref(b), ctypes.byref(v))
 
 
 class Context:
@@ -755,6 +821,31 @@ class Context:
         """kad_cstat_debug_route: the group width / long_min of the following cluster_resources() calls (0: the
         route's own). Measurement only."""
         self._chk(self.L.kad_cstat_debug_route(self.h, width, long_min))
+
+    def status_aggregate(self, kind: int, **arrays) -> dict:
+        """kad_status_aggregate → {sums[NV, O], changed[O]} and, Deployment, {observed[O]} or, Job, {start_min[O],
+        done_max[O], n_done[O], n_failed[O], finished[O]}. Arguments as :func:`sagg_args`
+        (statusagg.StatusAggBatch.arrays())."""
+        b, v, _keepalive, out = sagg_args(kind, **arrays)
+        self._chk(self.L.kad_status_aggregate(self.h, ctypes.byref(b), ctypes.byref(v)))
+        return out
+
+    def sagg_timing(self):
+        """kad_sagg_timing: device ms of the last status_aggregate() — (sagg_kernel,)."""
+        ms = (ctypes.c_float * 1)()
+        self._chk(self.L.kad_sagg_timing(self.h, ms))
+        return (float(ms[0]),)
+
+    def sagg_last_route(self) -> dict:
+        """kad_sagg_last_route: what the last status_aggregate() launched (sagg_route_eval's record)."""
+        out = (ctypes.c_int32 * len(SAGG_ROUTE))()
+        self._chk(self.L.kad_sagg_last_route(self.h, out))
+        return dict(zip(SAGG_ROUTE, out))
+
+    def sagg_debug_route(self, width: int = 0, long_min: int = 0) -> None:
+        """kad_sagg_debug_route: the group width / long_min of the following status_aggregate() calls (0: the
+        route's own). Measurement only."""
+        self._chk(self.L.kad_sagg_debug_route(self.h, width, long_min))
 
     def select_rows(self, rows: Sequence[Sequence[int]], max_clusters: Sequence[Optional[int]], flags: int = 0):
         """MaxCluster on explicit score rows → per row (status, sorted selected positions)."""

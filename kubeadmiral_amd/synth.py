@@ -1324,3 +1324,135 @@ def cluster_status_objects(a: dict, names=CSTAT_NAMES, scales=CSTAT_SCALES):
         cluster_nodes.append(nodes)
         cluster_pods.append(pods)
     return cluster_nodes, cluster_pods
+
+
+SAGG_BASE_TIME = 1_700_000_000  # Unix seconds
+
+
+def gen_status_aggregation(seed: int, kind: int, W: int, C: int, place_off=None, place_cluster=None, max_clusters: int = 5,
+                           nil_share: float = 0.02, stale_share: float = 0.05, duplicate_share: float = 0.0005,
+                           changed: float = 0.05):
+    """A synthetic status-aggregation batch as kad_status_aggregate's arrays: ``W`` source objects of ``kind``
+    (statusagg.DEPLOYMENT / JOB), one segment per placed member cluster. The placements are a scheduled batch's
+    (``place_off[W + 1]`` / ``place_cluster``: the results' CSR) or, without one, 1..``max_clusters`` clusters an
+    object; a share ``duplicate_share`` of the objects are Duplicate-mode workloads on every one of the ``C``
+    clusters. Members have partly ready replicas (Deployment) or are running, completed or failed (Job), a share
+    ``nil_share`` has a nil status, a share ``stale_share`` a synced generation behind the observed one. The old
+    status is the batch's own result except for a share ``changed`` of the objects. Returns (arrays — the keyword
+    arguments of Context.status_aggregate —, seg_cluster: the member cluster of every segment)."""
+    from . import statusagg as SA
+
+    rng = np.random.default_rng([seed, kind, 0x5A66])
+    if place_off is None:
+        nseg = rng.integers(1, max(1, min(max_clusters, C)) + 1, W)
+        first = (rng.random(W) * (C - nseg + 1)).astype(np.int64)
+    else:
+        nseg = np.diff(np.asarray(place_off, np.int64))
+        first = None
+    dup = rng.random(W) < duplicate_share
+    nseg = np.where(dup, C, nseg)
+    off = np.zeros(W + 1, np.int64)
+    off[1:] = np.cumsum(nseg)
+    S = int(off[-1])
+    owner = np.repeat(np.arange(W), nseg)
+    k = np.arange(S) - off[owner]
+    if first is not None:
+        seg_cluster = np.where(dup[owner], k, first[owner] + k).astype(np.int32)
+    else:
+        src = np.asarray(place_off, np.int64)[owner] + k
+        pc = np.asarray(place_cluster, np.int64)
+        seg_cluster = np.where(dup[owner], k, pc[np.minimum(src, max(0, len(pc) - 1))] if len(pc) else k).astype(np.int32)
+    nil = rng.random(S) < nil_share
+    obj_flags = np.where(rng.random(W) < 0.9, SA.OBJ_UPTODATE, 0).astype(np.uint8)
+    a = dict(kind=kind, obj_seg_off=off.astype(np.int32), obj_flags=obj_flags)
+    if kind == SA.DEPLOYMENT:
+        replicas = rng.integers(1, 101, S)
+        ready = (replicas * rng.uniform(0.5, 1.0, S)).astype(np.int64)
+        updated = np.maximum(ready, (replicas * rng.uniform(0.7, 1.0, S)).astype(np.int64))
+        a["seg_vals"] = np.where(nil, 0, np.stack([replicas, updated, ready, ready, replicas - ready])).astype(np.int32)
+        gen = rng.integers(1, 20, S)
+        a["seg_observed"] = np.where(nil, 0, gen).astype(np.int64)
+        a["seg_synced"] = np.where(nil, 0, np.where(rng.random(S) < stale_share, gen + 1, gen)).astype(np.int64)
+        a["seg_flags"] = np.where(nil, SA.SEG_NIL, SA.SEG_SYNCED).astype(np.uint8)
+        a["obj_generation"] = rng.integers(2, 50, W).astype(np.int64)
+        a["obj_observed"] = a["obj_generation"] - (rng.random(W) < 0.2)
+        a["old_vals"] = np.zeros((6, W), np.int64)
+    else:
+        cls = rng.random(S)
+        start = SAGG_BASE_TIME - rng.integers(0, 86400, S)
+        f = np.where(rng.random(S) < 0.97, SA.SEG_START, 0) | np.where(cls < 0.5, SA.SEG_DONE, np.where(cls < 0.6, SA.SEG_FAILED, 0))
+        a["seg_flags"] = np.where(nil, SA.SEG_NIL, f).astype(np.uint8)
+        a["seg_start"] = np.where((a["seg_flags"] & SA.SEG_START) != 0, start, 0).astype(np.int64)
+        a["seg_done"] = np.where((a["seg_flags"] & SA.SEG_DONE) != 0, start + rng.integers(1, 7200, S), 0).astype(np.int64)
+        done = (a["seg_flags"] & SA.SEG_DONE) != 0
+        a["seg_vals"] = np.where(nil, 0, np.stack([np.where(done, 0, rng.integers(0, 4, S)), np.where(done, rng.integers(1, 9, S), 0),
+                                                   rng.integers(0, 2, S)])).astype(np.int32)
+        a["old_vals"] = np.zeros((5, W), np.int64)
+    r = SA.sagg_numpy(**a)
+    nv = len(a["seg_vals"])
+    a["old_vals"][:nv] = r["sums"]
+    if kind == SA.DEPLOYMENT:
+        a["old_vals"][5] = r["observed"]
+        a["obj_observed"] = r["observed"].copy()  # one field of the source: its status.observedGeneration
+    else:
+        a["old_vals"][3] = r["start_min"]
+        a["old_vals"][4] = np.where((r["finished"] != 0) & (r["n_failed"] == 0), r["done_max"], SA.NO_DONE)
+    a["old_vals"][0, rng.random(W) < changed] += 1
+    return a, seg_cluster
+
+
+def status_aggregation_objects(a: dict, seg_cluster, names):
+    """The batch of :func:`gen_status_aggregation` as the controller sees it: per object the source object, its
+    federated object (template in step with the source, so that IsResourcePropagated holds where the object is
+    UPTODATE) and the member objects by cluster name (``names``: id → name). For small batches: tests. Returns
+    (sources, fed_objects, cluster_objs)."""
+    from . import statusagg as SA
+
+    kind = a["kind"]
+    off = a["obj_seg_off"]
+    sources, feds, members = [], [], []
+    for o in range(len(a["obj_flags"])):
+        old = a["old_vals"][:, o]
+        if kind == SA.DEPLOYMENT:
+            status = {k: float(v) for k, v in zip(SA.DEP_FIELDS + ("observedGeneration",), old) if v}
+            src = {"apiVersion": "apps/v1", "kind": "Deployment",
+                   "metadata": {"name": f"d{o}", "namespace": "default", "generation": int(a["obj_generation"][o])},
+                   "spec": {"replicas": 3}, "status": status}
+        else:
+            status = {k: int(v) for k, v in zip(SA.JOB_FIELDS, old) if v}
+            if old[3] != SA.NO_START:
+                status["startTime"] = SA.format_time(int(old[3]))
+            if old[4] != SA.NO_DONE:
+                status["completionTime"] = SA.format_time(int(old[4]))
+            src = {"apiVersion": "batch/v1", "kind": "Job", "metadata": {"name": f"j{o}", "namespace": "default", "generation": 1},
+                   "spec": {"parallelism": 2}, "status": status}
+        utd = bool(a["obj_flags"][o] & SA.OBJ_UPTODATE)
+        clusters, objs = [], {}
+        for s in range(int(off[o]), int(off[o + 1])):
+            name, f = names[int(seg_cluster[s])], int(a["seg_flags"][s])
+            vals = [int(v) for v in a["seg_vals"][:, s]]
+            if f & SA.SEG_NIL:
+                st = None
+            elif kind == SA.DEPLOYMENT:
+                st = dict(zip(SA.DEP_FIELDS, vals), observedGeneration=int(a["seg_observed"][s]))
+            else:
+                st = dict(zip(SA.JOB_FIELDS, vals))
+                if f & SA.SEG_START:
+                    st["startTime"] = SA.format_time(int(a["seg_start"][s]))
+                if f & SA.SEG_DONE:
+                    st["completionTime"] = SA.format_time(int(a["seg_done"][s]))
+                if f & SA.SEG_FAILED:
+                    st["conditions"] = [{"type": "Failed", "status": "True"}]
+            objs[name] = {"kind": src["kind"], "metadata": {"name": src["metadata"]["name"], "generation": 1}, "status": st}
+            if kind == SA.JOB or f & SA.SEG_SYNCED:
+                clusters.append({"name": name, "status": "OK",
+                                 "generation": int(a["seg_synced"][s]) if kind == SA.DEPLOYMENT else 1})
+        template = {k: v for k, v in src.items() if k != "status"}
+        fed = {"metadata": {"name": src["metadata"]["name"], "generation": 4,
+                            "annotations": {SA.OBSERVED_ANNOTATION_KEYS: "|", SA.OBSERVED_LABEL_KEYS: "|",
+                                            SA.TEMPLATE_MERGE_PATCH: '{"status":null}'}},
+               "spec": {"template": template}, "status": {"syncedGeneration": 4 if utd else 3, "clusters": clusters}}
+        sources.append(src)
+        feds.append(fed)
+        members.append(objs)
+    return sources, feds, members
