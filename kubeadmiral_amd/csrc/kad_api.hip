@@ -384,7 +384,8 @@ static int check_snapshot_header(kad_ctx* c, const kad_snapshot_header& h, size_
   return 0;
 }
 
-// SnapDev::fit_vals / fit_rows from the host shadow of the resources (clean snapshots, C <= FITFOLD_MAX_C)
+// SnapDev::fit_fences / fit_vals / fit_rows from the host shadow of the resources (clean snapshots,
+// C <= FITFOLD_MAX_C); every upload and update ends here (refresh_derived), so the three are rebuilt together
 static int build_fit_table(kad_ctx* c) {
   const int C = c->sd.C;
   c->sd.fitfold = 0;
@@ -406,9 +407,10 @@ static int build_fit_table(kad_ctx* c) {
   int mp = FIT_FENCES;  // vals padded with INT64_MAX to a power of two >= m + 1 (fence search)
   while (mp < c->sd.fit_m[0] + 1 || mp < c->sd.fit_m[1] + 1) mp *= 2;
   c->sd.fit_mp = mp;
+  words = (size_t)2 * FIT_FENCES;  // the fences lead the buffer (16-B aligned for prep's loads)
   for (int r = 0; r < 2; r++) words += (size_t)mp + ((size_t)c->sd.fit_m[r] + 1) * nch;
   c->h_fit.assign(words, 0);
-  size_t o = 0;
+  size_t o = (size_t)2 * FIT_FENCES;
   size_t vo[2], ro[2];
   for (int r = 0; r < 2; r++) {  // vals
     const int m = c->sd.fit_m[r];
@@ -418,6 +420,9 @@ static int build_fit_table(kad_ctx* c) {
     vo[r] = o;
     std::copy(u.begin(), u.end(), c->h_fit.begin() + (ptrdiff_t)o);
     std::fill(c->h_fit.begin() + (ptrdiff_t)(o + m), c->h_fit.begin() + (ptrdiff_t)(o + mp), INT64_MAX);
+    // fence i = value (i + 1) * S - 1: what prep's blocks used to gather from the values at every launch
+    const int S = mp / FIT_FENCES;
+    for (int i = 0; i < FIT_FENCES; i++) c->h_fit[(size_t)r * FIT_FENCES + i] = c->h_fit[o + (size_t)(i + 1) * S - 1];
     o += (size_t)mp;
   }
   for (int r = 0; r < 2; r++) {  // rows, from the largest amount down: row j = row j+1 | clusters at vals[j]
@@ -438,6 +443,7 @@ static int build_fit_table(kad_ctx* c) {
   HIPCHK(c, hipMemcpyAsync(c->d_fit.p, c->h_fit.data(), words * 8, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));  // h_fit may be rebuilt by the next upload / update
   const int64_t* d = static_cast<const int64_t*>(c->d_fit.p);
+  c->sd.fit_fences = d;
   for (int r = 0; r < 2; r++) {
     c->sd.fit_vals[r] = d + vo[r];
     c->sd.fit_rows[r] = reinterpret_cast<const uint64_t*>(d + ro[r]);

@@ -51,9 +51,12 @@ struct SnapDev {
   // (allocatable - used) ascending, then INT64_MAX up to fit_mp; fit_rows[r][j][nch]: clusters whose available
   // amount is >= fit_vals[r][j] (row m_r empty). prep_kernel ANDs row lower_bound(request) into the
   // static words, and the schedule kernels skip their own cpu / memory compare (SnapDev::fitfold).
+  // fit_fences[r][i] = fit_vals[r][(i + 1) * (fit_mp / FIT_FENCES) - 1], contiguous and 16-B aligned: the
+  // first levels of prep's rank search, built with the values at upload / update and copied to LDS per block.
   int fitfold;
   int fit_m[2];
   int fit_mp;  // fit_vals[r] length: a power of two >= FIT_FENCES, > fit_m[r] (INT64_MAX padding)
+  const int64_t* fit_fences;
   const int64_t* fit_vals[2];
   const uint64_t* fit_rows[2];
   const int64_t *alloc_cpu, *alloc_mem, *used_cpu, *used_mem, *alloc_s, *used_s, *alloc_cores, *avail_cores;

@@ -9,7 +9,7 @@ namespace kad {
 
 // One lane per (unit, PREP_CPL consecutive 64-cluster chunks), every launch,
 // before the schedule kernel:
-//  * the unit's first lane writes its 64-B UnitRec, routing units that use a
+//  * the unit's first lanes write its 64-B UnitRec (16 B each), routing units that use a
 //    feature the lean kernel leaves out (scalar resource requests, more than
 //    64 taint ids or GVKs, debug capture) to schedule_kernel (REC_FULL);
 //  * every lane writes the unit's static filter words for its chunks: the
@@ -242,8 +242,8 @@ __device__ __forceinline__ void folded_words(const SnapDev& s, uint32_t fm, uint
   }
 }
 
-// #(fit_vals[r] < x) for r = 0, 1 (x0, x1): 8 levels over the LDS fences (fence i = value (i+1)*S - 1,
-// S = fit_mp / FIT_FENCES), then log2(S) levels in global memory; both searches interleaved
+// #(fit_vals[r] < x) for r = 0, 1 (x0, x1): 8 levels over the LDS fences (SnapDev::fit_fences: fence i =
+// value (i+1)*S - 1, S = fit_mp / FIT_FENCES), then log2(S) levels in global memory; both searches interleaved
 __device__ __forceinline__ int2 fit_ranks(const SnapDev& s, const int64_t (*fences)[FIT_FENCES], int64_t x0, int64_t x1) {
   int f0 = 0, f1 = 0;
 #pragma unroll
@@ -283,34 +283,49 @@ __global__ __launch_bounds__(256, KAD_PREP_MINW) void prep_kernel(SnapDev s, Bat
   // and its loop cost C4's 2-lane units 17 us: profiles/r06/ab_c3_prep_persistent.txt)
   const bool live = g < (uint32_t)b.W * per;
   const uint32_t w = live ? g / per : 0u, l = g - w * per, ch0 = l * CPL;
-  // the unit's lanes load its program words 0 .. CPL*per-1 with coalesced
-  // loads into LDS: the interpreter's word → row chain then runs on LDS
-  // reads, not on dependent global loads
-  const int32_t fpo = live ? b.fprog_off[w] : 0;
-  const int32_t plen = live ? b.fprog_off[w + 1] - fpo : 0;
-#pragma unroll
-  for (int k = 0; k < CPL; k++) {
-    const int i = (int)ch0 + k;
-    prog_words[threadIdx.x * CPL + k] = i < plen ? b.fprog[fpo + i] : 0;
-  }
-  __shared__ int64_t fences[2][FIT_FENCES];  // SnapDev::fitfold: every S-th fit value per resource
+  if (b.W <= 0) return;  // (the one block of an empty batch: the resets above are all it does)
+  // every per-unit load is issued up front by every lane (the lanes of a unit share its cache lines), and
+  // before the barrier (none of them reads LDS): the batch columns and the program offsets are one round of
+  // loads in flight together with the fences, the program words and the toleration words (which wait for
+  // fprog_off and tolset) a second, and the record's chain and the affinity chain below overlap instead of
+  // running one after the other. The loads are unconditional (a select per load would become a branch and
+  // a wait per load): the last block's dead lanes read unit 0's columns.
+  const int32_t fpo = b.fprog_off[w], fpo1 = b.fprog_off[w + 1];
+  const int32_t plen = live ? fpo1 - fpo : 0;
+  // SnapDev::fitfold: every S-th fit value per resource, from the snapshot's fence table (built at upload /
+  // update): one coalesced 16-B load per lane, 4 KB per block
+  __shared__ __attribute__((aligned(16))) int64_t fences[2][FIT_FENCES];
+  static_assert(2 * FIT_FENCES % 512 == 0, "the fence copy moves 2 values per lane of a 256-lane block");
+  longlong2 fv[FIT_FENCES / 256];
   if (s.fitfold) {
-    const int S = s.fit_mp / FIT_FENCES;
-    for (int i = threadIdx.x; i < 2 * FIT_FENCES; i += 256)
-      fences[i / FIT_FENCES][i % FIT_FENCES] = s.fit_vals[i / FIT_FENCES][(i % FIT_FENCES + 1) * S - 1];
+#pragma unroll
+    for (int i = 0; i < FIT_FENCES / 256; i++) fv[i] = reinterpret_cast<const longlong2*>(s.fit_fences)[i * 256 + threadIdx.x];
   }
-  __syncthreads();
-  if (!live) return;
-  // every per-unit load is issued up front by every lane (the lanes of a
-  // unit share its cache lines), so the record lane's chain and the affinity
-  // chain below overlap instead of running one after the other
   const uint32_t f = b.flags[w];
   const uint32_t fm = p.filter_mask;
   const int32_t gvk = b.gvk[w], tolset = b.tolset[w], sprog = b.sprog_off[w];
   const int64_t rqc = b.req_cpu[w], rqm = b.req_mem[w], maxc = b.maxc[w], desired = b.desired[w];
   const int64_t oo = b.out_off[w];
   const int32_t so0 = b.sreq_off[w], so1 = b.sreq_off[w + 1];
+  // the unit's lanes load its program words 0 .. CPL*per-1 with coalesced loads into LDS: the interpreter's
+  // word → row chain then runs on LDS reads, not on dependent global loads (words past the program read
+  // the unit's word 0 and are stored as 0)
+  int32_t pwv[CPL];
+#pragma unroll
+  for (int k = 0; k < CPL; k++) {
+    const int i = (int)ch0 + k;
+    const int32_t v = b.fprog[fpo + (i < plen ? i : 0)];
+    pwv[k] = i < plen ? v : 0;
+  }
   const uint64_t tol0 = b.tol_all[(size_t)tolset * b.TW], tolp0 = b.tol_pns[(size_t)tolset * b.TW];
+  if (s.fitfold) {
+#pragma unroll
+    for (int i = 0; i < FIT_FENCES / 256; i++) reinterpret_cast<longlong2*>(&fences[0][0])[i * 256 + threadIdx.x] = fv[i];
+  }
+#pragma unroll
+  for (int k = 0; k < CPL; k++) prog_words[threadIdx.x * CPL + k] = pwv[k];
+  __syncthreads();
+  if (!live) return;
   bool full = force_full != 0;
   // the unfolded schedule kernels cache GVK word 0 only; folded snapshots take every GVK id from the slices
   if ((fm & (1u << KAD_PL_API_RESOURCES)) && gvk >= 64 && !s.fold) full = true;
@@ -384,21 +399,26 @@ __global__ __launch_bounds__(256, KAD_PREP_MINW) void prep_kernel(SnapDev s, Bat
     route = act && !(rflags & REC_FULL) && !(f & KAD_W_WIDE_SCORES) && (uint64_t)rqc < (1ull << 46) &&
             (uint64_t)rqm < (1ull << 46) && cnt > WIDE_P;
   }
-  if (l == 0) {
-    UnitRec r;
-    r.flags = rflags | (route ? REC_ROW : 0u);
-    r.gvk = gvk;
-    r.tolset = tolset;
-    r.sprog_off = sprog;
-    r.req_cpu = rqc;
-    r.req_mem = rqm;
-    r.maxc = maxc;
-    r.out_off = oo;
-    r.tol0 = tol0;
-    r.tolp0 = tolp0;
-    b.rec[w] = r;
-    if (route) b.rows[atomicAdd(b.rows_n, 1)] = (int32_t)w;
+  // the record is stored by the unit's lanes, 16-B piece q by lane q (every lane holds every column, and
+  // route is the same in all of them): with 4 or more lanes per unit a wave's store writes one contiguous
+  // 1 KB (C3: 16 units), where the first lane alone took four stores of 16 lanes at a 64-B stride. 3 lanes:
+  // the third stores two pieces; 2 lanes: two each; 1 lane: the whole record, as before.
+  const auto u64x2 = [](uint64_t a, uint64_t c) { return make_uint4((uint32_t)a, (uint32_t)(a >> 32), (uint32_t)c, (uint32_t)(c >> 32)); };
+  const uint4 p0 = make_uint4(rflags | (route ? REC_ROW : 0u), (uint32_t)gvk, (uint32_t)tolset, (uint32_t)sprog);
+  const uint4 p1 = u64x2((uint64_t)rqc, (uint64_t)rqm), p2 = u64x2((uint64_t)maxc, (uint64_t)oo), p3 = u64x2(tol0, tolp0);
+  const auto sel = [](bool c, const uint4& a, const uint4& o) { return make_uint4(c ? a.x : o.x, c ? a.y : o.y, c ? a.z : o.z, c ? a.w : o.w); };
+  const auto pick = [&](uint32_t q) { return sel(q < 2, sel(q == 0, p0, p1), sel(q == 2, p2, p3)); };
+  uint4* rp = reinterpret_cast<uint4*>(b.rec + w);
+  if (per >= 3) {
+    if (l < 4) rp[l] = pick(l);
+    if (per == 3 && l == 2) rp[3] = p3;
+  } else if (per == 2) {
+    rp[2 * l] = sel(l == 0, p0, p2);
+    rp[2 * l + 1] = sel(l == 0, p1, p3);
+  } else {
+    rp[0] = p0, rp[1] = p1, rp[2] = p2, rp[3] = p3;
   }
+  if (l == 0 && route) b.rows[atomicAdd(b.rows_n, 1)] = (int32_t)w;
 }
 
 // prep_wave_kernel<CW> — prep_kernel for wide snapshots (64 < ceil(C/64) <= 64*CW chunks, C5's 10 000
@@ -422,16 +442,11 @@ __global__ __launch_bounds__(256) void prep_wave_kernel(SnapDev s, BatchDev b, P
     }
   }
   if (g < (uint32_t)WQ_HEADS) b.wq[g * WQ_STRIDE] = 0u;
-  __shared__ int64_t fences[2][FIT_FENCES];
+  __shared__ __attribute__((aligned(16))) int64_t fences[2][FIT_FENCES];  // the snapshot's fence table, 16 B per lane
   if (s.fitfold) {
-    const int S = s.fit_mp / FIT_FENCES;
-    const int64_t* fv0 = s.fit_vals[0];
-    const int64_t* fv1 = s.fit_vals[1];
-    for (int i = threadIdx.x; i < FIT_FENCES; i += 256) {
-      const int64_t a0 = fv0[(i + 1) * S - 1], a1 = fv1[(i + 1) * S - 1];
-      fences[0][i] = a0;
-      fences[1][i] = a1;
-    }
+    const longlong2* src = reinterpret_cast<const longlong2*>(s.fit_fences);
+    longlong2* dst = reinterpret_cast<longlong2*>(&fences[0][0]);
+    for (int i = threadIdx.x; i < FIT_FENCES; i += 256) dst[i] = src[i];
   }
   __syncthreads();
   // one unit per wave, grid = units / 4 (a unit loop here, even at one trip per wave, took C5's prep
