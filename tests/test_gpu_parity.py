@@ -166,7 +166,8 @@ def test_golden_planner_on_gpu(ctx, c, path, monkeypatch):
 @pytest.mark.parametrize("seed", range(6))
 def test_plan_rows_lanes_equal_workspace(ctx, seed, monkeypatch):
     """Random rows (K 1..64, weights/minimums/maximums/capacities/current replicas incl. zero, tie-heavy
-    hashes, avoid/keep both ways): the register planner and the LDS-workspace planner agree exactly."""
+    hashes, avoid/keep both ways): the register planner and the LDS-workspace planner agree exactly, and with
+    the row reference (plan_ref.py: the Python oracle's getDesiredPlan)."""
     rng = np.random.default_rng(seed)
     rows = []
     for _ in range(300):
@@ -181,6 +182,9 @@ def test_plan_rows_lanes_equal_workspace(ctx, seed, monkeypatch):
                           "current": int(rng.integers(0, 400)) if rng.random() < 0.5 else 0})
         rows.append({"elems": elems, "total": int(rng.integers(0, 20_000)), "avoid": bool(rng.random() < 0.5),
                      "keep": bool(rng.random() < 0.5)})
+    import plan_cases
+    import plan_ref
+    assert all(plan_cases.admissible(r) for r in rows)  # non-negative, no wrap, within the reference's round guard
     lanes = ctx.plan_rows(rows)
     ctx.plan_force_workspace(True)
     try:
@@ -188,6 +192,7 @@ def test_plan_rows_lanes_equal_workspace(ctx, seed, monkeypatch):
     finally:
         ctx.plan_force_workspace(False)
     assert lanes == ws
+    assert lanes == plan_ref.plan_rows(rows)
 
 
 @pytest.mark.parametrize("seed", range(8))
@@ -196,7 +201,7 @@ def test_plan_rows_pairs_equal_lanes(ctx, seed):
     planner on random rows: K 1..40 (pairs with one row past 32 fall back to one row per wave), tie-heavy
     hashes, weights up to 2^26 on some rows (the non-kbuf rank path), totals past 2^24 on some rows (the
     int64 desired-plan path beside a narrow row), minimums / maximums / capacities / current replicas,
-    avoid / keep both ways."""
+    avoid / keep both ways. Both equal the row reference (plan_ref.py)."""
     rng = np.random.default_rng(700 + seed)
     rows = []
     for _ in range(400):
@@ -214,6 +219,9 @@ def test_plan_rows_pairs_equal_lanes(ctx, seed):
         total = int(rng.integers(0, 20_000)) if rng.random() < 0.95 else int(rng.integers(1 << 24, 1 << 30))
         rows.append({"elems": elems, "total": total, "avoid": bool(rng.random() < 0.5),
                      "keep": bool(rng.random() < 0.5)})
+    import plan_cases
+    import plan_ref
+    assert all(plan_cases.admissible(r) for r in rows)  # non-negative, no wrap, within the reference's round guard
     lanes = ctx.plan_rows(rows)
     ctx.plan_force_workspace(2)
     try:
@@ -221,6 +229,7 @@ def test_plan_rows_pairs_equal_lanes(ctx, seed):
     finally:
         ctx.plan_force_workspace(0)
     assert pairs == lanes
+    assert lanes == plan_ref.plan_rows(rows)
 
 
 @pytest.mark.parametrize("c", RSP, ids=[case_id(c) for c in RSP])
