@@ -958,6 +958,96 @@ int kad_sagg_route_eval(int32_t n_objects, int32_t n_long, int64_t short_segment
 int kad_sagg_last_route(kad_ctx* ctx, int32_t* out);
 int kad_sagg_debug_route(kad_ctx* ctx, int32_t force_width, int32_t force_long_min);
 
+/* ------------------------------------------------------ rollout planning
+ * While a Deployment rolls out across member clusters the sync controller asks, per member cluster, which replicas,
+ * maxSurge and maxUnavailable it may be given now, so that the federation as a whole stays inside the template's
+ * own maxSurge / maxUnavailable (RolloutPlanner.Plan, pkg/controllers/util/rolloutplan.go:569-695, driven by
+ * pkg/controllers/sync/dispatch/managed.go:160-323). kad_rollout_plan does that for a batch of objects.
+ *
+ * obj_tgt_off[O + 1] are an object's targets, one per member cluster, SORTED BY CLUSTER NAME in byte order (the
+ * order the budgets are handed out in; the library cannot check it).
+ * Per object: obj_max_surge[O] / obj_max_unavailable[O] = the template's resolved fenceposts, obj_replicas[O] =
+ * the replicas over the selected clusters (NewRolloutPlanner, :459-487); obj_flags[O]: KAD_ROLLOUT_OBJ_ERROR = the
+ * caller found a host-side error: nothing is computed, the status is KAD_ROLLOUT_ST_ERROR and no target is planned.
+ * Per target: tgt_vals[KAD_ROLLOUT_NV][T], row-major int32: TargetStatus' Replicas, ActualReplicas,
+ * AvailableReplicas, UpdatedReplicas, UpdatedAvailableReplicas, CurrentNewReplicas, CurrentNewAvailableReplicas,
+ * MaxSurge, MaxUnavailable (:166-177), then DesiredReplicas; tgt_flags[T]: KAD_ROLLOUT_TGT_UPDATED = Status.Updated,
+ * KAD_ROLLOUT_TGT_EXISTS = the member object is not nil (without it the status rows are 0, :367-372),
+ * KAD_ROLLOUT_TGT_TO_DELETE = the cluster is no longer selected (DesiredReplicas is 0).
+ *
+ * Outputs per target: plan_flags[T]: KAD_ROLLOUT_PLAN_PLANNED = the cluster has a plan; _HAS_REPLICAS / _HAS_SURGE /
+ * _HAS_UNAVAILABLE = the plan's field is not nil, its value in replicas[T] / max_surge[T] / max_unavailable[T] (0
+ * otherwise); _ONLY_PATCH_REPLICAS. action[T] = the dispatch operation of managed.go:219-249, KAD_ROLLOUT_ACT_*.
+ * Per object: status[O]: KAD_ROLLOUT_ST_OK; _SCALE = PlanScale (every target planned, every field nil); _INVALID =
+ * validatePlans failed (no target planned); _ERROR. All arithmetic is Go's int32 and wraps.
+ *
+ * Everything is validated on the host before anything is launched (KAD_EINVAL): the counts, the offsets, unknown
+ * flags, a target without EXISTS that is UPDATED, TO_DELETE or has a non-zero status, a target TO_DELETE with
+ * DesiredReplicas != 0. Runs on the ctx stream (rollout_kernel: kad_rollout.hip); blocks until the outputs are in
+ * the caller's buffers. Needs no snapshot and reads no resident state, so a kad_group member accepts it. Leaves the
+ * last results, the timings and any later kad_schedule as they were. n_objects == 0 returns 0 without launching. */
+#define KAD_ROLLOUT_NV 10
+#define KAD_ROLLOUT_OBJ_ERROR 1u
+#define KAD_ROLLOUT_TGT_UPDATED 1u
+#define KAD_ROLLOUT_TGT_EXISTS 2u
+#define KAD_ROLLOUT_TGT_TO_DELETE 4u
+#define KAD_ROLLOUT_PLAN_PLANNED 1u
+#define KAD_ROLLOUT_PLAN_HAS_REPLICAS 2u
+#define KAD_ROLLOUT_PLAN_HAS_SURGE 4u
+#define KAD_ROLLOUT_PLAN_HAS_UNAVAILABLE 8u
+#define KAD_ROLLOUT_PLAN_ONLY_PATCH_REPLICAS 16u
+#define KAD_ROLLOUT_ACT_KEEP_TEMPLATE_PATCH 0 /* not planned, the member object exists: patch, keep its template */
+#define KAD_ROLLOUT_ACT_NONE 1                /* not planned and no member object */
+#define KAD_ROLLOUT_ACT_DELETE 2
+#define KAD_ROLLOUT_ACT_CREATE 3
+#define KAD_ROLLOUT_ACT_PATCH_REPLICAS 4      /* patch with the planned replicas, keep its template */
+#define KAD_ROLLOUT_ACT_UPDATE 5
+#define KAD_ROLLOUT_ST_OK 0
+#define KAD_ROLLOUT_ST_SCALE 1
+#define KAD_ROLLOUT_ST_INVALID 2
+#define KAD_ROLLOUT_ST_ERROR 3
+typedef struct kad_rollout_batch {
+  int32_t n_objects; /* O */
+  int32_t n_targets; /* T */
+  const int32_t* obj_tgt_off;         /* [O + 1] */
+  const int32_t* obj_max_surge;       /* [O] */
+  const int32_t* obj_max_unavailable; /* [O] */
+  const int32_t* obj_replicas;        /* [O] */
+  const uint8_t* obj_flags;           /* [O] KAD_ROLLOUT_OBJ_* */
+  const int32_t* tgt_vals;            /* [KAD_ROLLOUT_NV * T] */
+  const uint8_t* tgt_flags;           /* [T] KAD_ROLLOUT_TGT_* */
+} kad_rollout_batch;
+typedef struct kad_rollout_view {
+  int32_t* replicas;        /* [T] */
+  int32_t* max_surge;       /* [T] */
+  int32_t* max_unavailable; /* [T] */
+  uint8_t* plan_flags;      /* [T] KAD_ROLLOUT_PLAN_* */
+  uint8_t* action;          /* [T] KAD_ROLLOUT_ACT_* */
+  uint8_t* status;          /* [O] KAD_ROLLOUT_ST_* */
+} kad_rollout_view;
+int kad_rollout_plan(kad_ctx* ctx, const kad_rollout_batch* batch, const kad_rollout_view* out);
+/* Host only (no device, no ctx): the same validation. nowrap[O] (may be null) receives 1 for every object whose
+ * inputs' absolute values sum to less than 2^29: nothing in Plan() can wrap int32 there and the device plans it
+ * with prefix sums; the other objects are walked serially in wrapping arithmetic, with the same results. */
+int kad_rollout_check(const kad_rollout_batch* batch, const kad_rollout_view* out, uint8_t* nowrap);
+/* Device time of the last kad_rollout_plan that launched, from HIP events: ms[0] = rollout_kernel. */
+int kad_rollout_timing(kad_ctx* ctx, float ms[1]);
+/* What a kad_rollout_plan launches, as the library's one decision computes it (csrc/kad_rollout.h route_rollout; no
+ * device work, no ctx) for n_objects objects, n_long of them (not in error) with more targets than the route's
+ * long_min, the other objects that are not in error holding short_targets targets, n_serial objects on the serial
+ * walk: out[KAD_ROLLOUT_ROUTE_FIELDS] is [0] the lanes per object of the group path (the mean targets per short
+ * object rounded up to a power of two in [1, 64]), [1] long_min, [2] block threads, [3] blocks of the group path,
+ * [4] blocks of the long path (four long objects each, one per wave), [5] objects between two consecutive objects
+ * of one lane group, [6] n_serial. kad_rollout_last_route: the same record for the last kad_rollout_plan that
+ * launched (KAD_ESTATE before one). force_width (a power of two in [1, 64]) / force_long_min of
+ * kad_rollout_debug_route (0: the route's own) replace [0] and [1] for the following calls on this ctx;
+ * force_serial = 1 walks every object serially. Measurement / tests only. */
+#define KAD_ROLLOUT_ROUTE_FIELDS 7
+int kad_rollout_route_eval(int32_t n_objects, int32_t n_long, int64_t short_targets, int32_t n_serial, int32_t n_cu,
+                           int32_t* out);
+int kad_rollout_last_route(kad_ctx* ctx, int32_t* out);
+int kad_rollout_debug_route(kad_ctx* ctx, int32_t force_width, int32_t force_long_min, int32_t force_serial);
+
 /* ------------------------------------------------ result application (§8 f3)
  * applySchedulingResult (pkg/controllers/scheduler/scheduler.go:632-695) writes a unit's result into its
  * federated object: the scheduler controller's placement (util.SetPlacementClusterNames,

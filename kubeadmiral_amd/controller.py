@@ -492,6 +492,37 @@ class BatchReconciler:
                 out[i] = StatusAggOutcome(STATUS_ERROR if err else STATUS_ALL_OK, need, str(err) if err else None)
         return out  # type: ignore[return-value]
 
+    # ------------------------------------------------------------------ rollout planning
+    def reconcile_rollout(self, objs: Sequence[dict], member_objs: Sequence[Dict[str, Optional[dict]]],
+                          selected: Sequence, controller_order: Sequence[str] = ()) -> list:
+        """The managed dispatcher's rollout planning for a batch of federated objects
+        (pkg/controllers/sync/dispatch/managed.go:203-250): ``objs[i]`` is a federated Deployment,
+        ``member_objs[i]`` its copy (or None) in every ready member cluster it could be fetched from and
+        ``selected[i]`` the clusters its placement selects. One kad_rollout_plan answers every object
+        (rollout.RolloutBatch); returns per object a rollout.RolloutOutcome with the plans, the overrides
+        (GetRolloutOverrides), the dispatch action of every cluster and the status, or None for an object the
+        planner does not see: the type config's RolloutPlan is not enabled, or spec.retainReplicas is true. A host
+        error (an unsupported kind, replicas or annotations missing) makes the object ST_ERROR: its existing
+        member objects are patched with their template kept. Dispatching stays with the caller."""
+        from . import rollout as RO
+
+        out: list = [None] * len(objs)
+        if not getattr(self.type_config, "rollout_plan", False):
+            return out
+        batch, index = RO.RolloutBatch(self.type_config, controller_order), []
+        for i, (fed, members, sel) in enumerate(zip(objs, member_objs, selected)):
+            try:
+                if RO.check_retain_replicas(fed):
+                    continue
+            except RO.RolloutError:  # CheckRetainReplicasFailed: Dispatch returns without dispatching
+                continue
+            batch.add(fed, members, sel)
+            index.append(i)
+        if index:
+            for i, o in zip(index, batch.apply(self.ctx.rollout_plan(**batch.arrays()))):
+                out[i] = o
+        return out
+
     # ------------------------------------------------------------------ the reconcile over JSON texts
     def reconcile_texts(self, texts: Sequence, policies: Sequence, clusters: List[T.FederatedCluster],
                         profiles: Optional[Dict[str, Optional[dict]]] = None

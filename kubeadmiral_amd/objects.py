@@ -193,6 +193,8 @@ class FederatedTypeConfig:
     replicas_spec: str = ""      # Spec.PathDefinition.ReplicasSpec, dot path under the template
     replicas_status: str = ""        # Spec.PathDefinition.ReplicasStatus (auto migration: total replicas)
     ready_replicas_status: str = ""  # Spec.PathDefinition.ReadyReplicasStatus (auto migration: ready replicas)
+    available_replicas_status: str = ""  # Spec.PathDefinition.AvailableReplicasStatus (rollout planning)
+    rollout_plan: bool = False       # Spec.RolloutPlan == Enabled (extensions_federatedtypeconfig.go:90-92)
 
     @property
     def namespaced(self) -> bool:

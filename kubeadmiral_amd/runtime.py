@@ -120,6 +120,18 @@ class SaggView(ctypes.Structure):  # kad_sagg_view
                 ("n_failed", ctypes.c_void_p), ("finished", ctypes.c_void_p)]
 
 
+class RolloutBatch(ctypes.Structure):  # kad_rollout_batch
+    _fields_ = [("n_objects", ctypes.c_int32), ("n_targets", ctypes.c_int32), ("obj_tgt_off", ctypes.c_void_p),
+                ("obj_max_surge", ctypes.c_void_p), ("obj_max_unavailable", ctypes.c_void_p),
+                ("obj_replicas", ctypes.c_void_p), ("obj_flags", ctypes.c_void_p), ("tgt_vals", ctypes.c_void_p),
+                ("tgt_flags", ctypes.c_void_p)]
+
+
+class RolloutView(ctypes.Structure):  # kad_rollout_view
+    _fields_ = [("replicas", ctypes.c_void_p), ("max_surge", ctypes.c_void_p), ("max_unavailable", ctypes.c_void_p),
+                ("plan_flags", ctypes.c_void_p), ("action", ctypes.c_void_p), ("status", ctypes.c_void_p)]
+
+
 _lib = None
 
 
@@ -244,6 +256,14 @@ def load_library(path: str = LIB_PATH):
         L.kad_sagg_route_eval.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, P]
         L.kad_sagg_last_route.argtypes = [P, P]
         L.kad_sagg_debug_route.argtypes = [P, ctypes.c_int32, ctypes.c_int32]
+    if hasattr(L, "kad_rollout_plan"):
+        L.kad_rollout_plan.argtypes = [P, P, P]
+        L.kad_rollout_check.argtypes = [P, P, P]
+        L.kad_rollout_timing.argtypes = [P, P]
+        L.kad_rollout_route_eval.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32,
+                                             ctypes.c_int32, P]
+        L.kad_rollout_last_route.argtypes = [P, P]
+        L.kad_rollout_debug_route.argtypes = [P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
     L.kad_debug_inject_fault.argtypes = [P, I]
     L.kad_debug_plan_force_workspace.argtypes = [P, I]
     L.kad_trigger_suffix_upload.argtypes = [P, P, SZ]
@@ -494,6 +514,46 @@ def sagg_check(kind: int, **arrays) -> int:
     code."""
     b, v, _keepalive, _ = sagg_args(kind, **arrays)
     return load_library().kad_sagg_check(ctypes.byref(b), ctypes.byref(v))
+
+
+ROLLOUT_ROUTE = ("width", "long_min", "threads", "grid", "long_grid", "stride", "serial")
+ROLLOUT_NV = 10  # int32 rows of tgt_vals
+
+
+def rollout_route_eval(n_objects: int, n_long: int, short_targets: int, n_serial: int = 0, n_cu: int = 256) -> dict:
+    """kad_rollout_route_eval: the launch decision of a rollout_plan (needs no GPU)."""
+    out = (ctypes.c_int32 * len(ROLLOUT_ROUTE))()
+    rc = load_library().kad_rollout_route_eval(n_objects, n_long, short_targets, n_serial, n_cu, out)
+    if rc != 0:
+        raise ValueError(f"kad_rollout_route_eval: {rc}")
+    return dict(zip(ROLLOUT_ROUTE, out))
+
+
+_ROLLOUT_IN = (("obj_tgt_off", np.int32), ("obj_max_surge", np.int32), ("obj_max_unavailable", np.int32),
+               ("obj_replicas", np.int32), ("obj_flags", np.uint8), ("tgt_vals", np.int32), ("tgt_flags", np.uint8))
+_ROLLOUT_OUT = (("replicas", np.int32, 1), ("max_surge", np.int32, 1), ("max_unavailable", np.int32, 1),
+                ("plan_flags", np.uint8, 1), ("action", np.uint8, 1), ("status", np.uint8, 0))
+
+
+def rollout_args(**arrays):
+    """The kad_rollout_batch / kad_rollout_view of one call with the arrays that back them (the batch's fields by
+    name; the counts are taken from obj_flags and tgt_flags as they are, so that a malformed batch reaches the
+    library's validation). Returns (batch, view, the input arrays, the output arrays by name)."""
+    a = {k: np.ascontiguousarray(arrays[k], dt).reshape(-1) for k, dt in _ROLLOUT_IN if k in arrays}
+    n = (len(a["obj_flags"]), len(a["tgt_flags"]))
+    out = {k: np.zeros(max(1, n[dim]), dt) for k, dt, dim in _ROLLOUT_OUT}
+    b = RolloutBatch(n[0], n[1], *(a[k].ctypes.data if k in a and len(a[k]) else None for k, _ in _ROLLOUT_IN))
+    v = RolloutView(*(out[k].ctypes.data for k, _, _ in _ROLLOUT_OUT))
+    return b, v, a, {k: out[k][:n[dim]] for k, _, dim in _ROLLOUT_OUT}
+
+
+def rollout_check(**arrays):
+    """kad_rollout_check: kad_rollout_plan's validation of :func:`rollout_args` arguments; no GPU. Returns (the code,
+    nowrap[O]: the objects the device plans with prefix sums)."""
+    b, v, _keepalive, _ = rollout_args(**arrays)
+    nowrap = np.zeros(max(1, b.n_objects), np.uint8)
+    rc = load_library().kad_rollout_check(ctypes.byref(b), ctypes.byref(v), nowrap.ctypes.data)
+    return rc, nowrap[:max(0, b.n_objects)]
 
 
 class Context:
@@ -846,6 +906,30 @@ class Context:
         """kad_sagg_debug_route: the group width / long_min of the following status_aggregate() calls (0: the
         route's own). Measurement only."""
         self._chk(self.L.kad_sagg_debug_route(self.h, width, long_min))
+
+    def rollout_plan(self, **arrays) -> dict:
+        """kad_rollout_plan → {replicas[T], max_surge[T], max_unavailable[T], plan_flags[T], action[T], status[O]}.
+        Arguments as :func:`rollout_args` (rollout.RolloutBatch.arrays())."""
+        b, v, _keepalive, out = rollout_args(**arrays)
+        self._chk(self.L.kad_rollout_plan(self.h, ctypes.byref(b), ctypes.byref(v)))
+        return out
+
+    def rollout_timing(self):
+        """kad_rollout_timing: device ms of the last rollout_plan() — (rollout_kernel,)."""
+        ms = (ctypes.c_float * 1)()
+        self._chk(self.L.kad_rollout_timing(self.h, ms))
+        return (float(ms[0]),)
+
+    def rollout_last_route(self) -> dict:
+        """kad_rollout_last_route: what the last rollout_plan() launched (rollout_route_eval's record)."""
+        out = (ctypes.c_int32 * len(ROLLOUT_ROUTE))()
+        self._chk(self.L.kad_rollout_last_route(self.h, out))
+        return dict(zip(ROLLOUT_ROUTE, out))
+
+    def rollout_debug_route(self, width: int = 0, long_min: int = 0, serial: int = 0) -> None:
+        """kad_rollout_debug_route: the group width / long_min of the following rollout_plan() calls (0: the
+        route's own); serial = 1 walks every object serially. Measurement only."""
+        self._chk(self.L.kad_rollout_debug_route(self.h, width, long_min, serial))
 
     def select_rows(self, rows: Sequence[Sequence[int]], max_clusters: Sequence[Optional[int]], flags: int = 0):
         """MaxCluster on explicit score rows → per row (status, sorted selected positions)."""

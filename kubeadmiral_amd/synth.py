@@ -1456,3 +1456,86 @@ def status_aggregation_objects(a: dict, seg_cluster, names):
         feds.append(fed)
         members.append(objs)
     return sources, feds, members
+
+
+ROLLOUT_FENCEPOSTS = ((0, 25), (25, 0), (25, 25), (10, 5))  # the template's (maxSurge %, maxUnavailable %)
+
+
+def gen_rollout(seed: int, W: int, min_targets: int = 1, max_targets: int = 15, unchanged: float = 0.6,
+                updated: float = 0.5, deviation: float = 0.1):
+    """A synthetic rollout-planning batch as kad_rollout_plan's arrays (the keyword arguments of
+    Context.rollout_plan): ``W`` federated Deployments in the middle of a rollout, each on ``min_targets`` ..
+    ``max_targets`` member clusters (uniform; mean 8 by default). The template's fenceposts are one of
+    ROLLOUT_FENCEPOSTS as percentages of the desired total, resolved as the reference resolves them (surge up,
+    unavailable down, both zero: unavailable 1). A share ``unchanged`` of the targets keeps its size, the others are
+    to grow or shrink by up to a third; a share ``updated`` already runs the new template, with a new replica set
+    somewhere between empty and complete; a share ``deviation`` has one or two pods more or less than its spec, or
+    not available. Every member object exists and none is to delete."""
+    rng = np.random.default_rng([seed, 0x726F])
+    n = rng.integers(min_targets, max_targets + 1, W)
+    off = np.zeros(W + 1, np.int64)
+    off[1:] = np.cumsum(n)
+    T = int(off[-1])
+    owner = np.repeat(np.arange(W), n)
+    desired = rng.integers(0, 61, T)
+    keep = rng.random(T) < unchanged
+    delta = (desired * rng.uniform(-0.33, 0.33, T)).astype(np.int64)
+    replicas = np.where(keep, desired, np.maximum(desired + delta, 0))
+    upd = rng.random(T) < updated
+    progress = rng.random(T)
+    new = np.where(upd, np.where(progress < 0.4, replicas, (replicas * progress).astype(np.int64)), replicas)
+    new_avail = np.where(upd, np.maximum(new - rng.integers(0, 3, T), 0), new)
+    dev = rng.random(T) < deviation
+    actual = np.maximum(replicas + np.where(dev, rng.integers(-1, 3, T), 0), 0)
+    available = np.maximum(np.minimum(actual, replicas) - np.where(dev, rng.integers(0, 3, T), 0), 0)
+    total = np.bincount(owner, weights=desired, minlength=W).astype(np.int64)
+    fp = np.array(ROLLOUT_FENCEPOSTS, np.int64)[rng.integers(0, len(ROLLOUT_FENCEPOSTS), W)]
+    p_ms = -((-fp[:, 0] * total) // 100)
+    p_mu = (fp[:, 1] * total) // 100
+    p_mu = np.where((p_ms == 0) & (p_mu == 0), 1, p_mu)
+    # a member runs with what an earlier plan gave it: a share of the template's fenceposts
+    share = rng.uniform(0.0, 0.6, T)
+    ms = np.where(upd, (p_ms[owner] * share).astype(np.int64), 0)
+    mu = np.where(upd, (p_mu[owner] * share).astype(np.int64), 0)
+    mu = np.where((ms == 0) & (mu == 0), 1, mu)
+    vals = np.stack([replicas, actual, available, np.where(upd, new, 0), np.where(upd, new_avail, 0), new, new_avail,
+                     ms, mu, desired]).astype(np.int32)
+    return dict(obj_tgt_off=off.astype(np.int32), obj_max_surge=p_ms.astype(np.int32),
+                obj_max_unavailable=p_mu.astype(np.int32), obj_replicas=total.astype(np.int32),
+                obj_flags=np.zeros(W, np.uint8), tgt_vals=vals, tgt_flags=np.where(upd, 3, 2).astype(np.uint8))
+
+
+def rollout_objects(a, names):
+    """The objects behind a :func:`gen_rollout` batch, for the object-level path: per object the federated Deployment
+    (template, replicas overrides, current-revision annotation), its member Deployments by cluster name (an object's
+    k-th target is on ``names[k]``, which must be sorted) and the selected clusters."""
+    off = np.asarray(a["obj_tgt_off"], np.int64)
+    v = np.asarray(a["tgt_vals"], np.int64)
+    feds, members, selected = [], [], []
+    for o in range(len(off) - 1):
+        lo, hi = int(off[o]), int(off[o + 1])
+        strategy = {"rollingUpdate": {"maxSurge": int(a["obj_max_surge"][o]), "maxUnavailable": int(a["obj_max_unavailable"][o])}}
+        feds.append({"apiVersion": "types.kubeadmiral.io/v1alpha1", "kind": "FederatedDeployment",
+                     "metadata": {"name": f"dp-{o}", "namespace": "default",
+                                  "annotations": {"kubeadmiral.io/current-revision": "rev-new"}},
+                     "spec": {"template": {"spec": {"replicas": 1, "strategy": strategy}},
+                              "overrides": [{"controller": "kubeadmiral.io/global-scheduler", "clusters": [
+                                  {"clusterName": names[i - lo], "patches": [{"path": "/spec/replicas", "value": float(v[9, i])}]}
+                                  for i in range(lo, hi)]}]}})
+        objs = {}
+        for i in range(lo, hi):
+            updated = bool(int(a["tgt_flags"][i]) & 1)
+            objs[names[i - lo]] = {
+                "apiVersion": "apps/v1", "kind": "Deployment",
+                "metadata": {"name": f"dp-{o}", "namespace": "default", "annotations": {
+                    "kubeadmiral.io/current-revision": "rev-new" if updated else "rev-old",
+                    "latestreplicaset.kubeadmiral.io/name": f"dp-{o}-rs", "latestreplicaset.kubeadmiral.io/replicas": str(int(v[5, i])),
+                    "latestreplicaset.kubeadmiral.io/available-replicas": str(int(v[6, i]))}},
+                "spec": {"replicas": int(v[0, i]),
+                         "strategy": {"rollingUpdate": {"maxSurge": int(v[7, i]), "maxUnavailable": int(v[8, i])}}},
+                "status": {"replicas": int(v[1, i]), "availableReplicas": int(v[2, i])}}
+        feds[-1]["spec"]["template"]["spec"]["replicas"] = 1
+        members.append(objs)
+        selected.append(set(objs))
+    return feds, members, selected
+
