@@ -1048,6 +1048,125 @@ int kad_rollout_route_eval(int32_t n_objects, int32_t n_long, int64_t short_targ
 int kad_rollout_last_route(kad_ctx* ctx, int32_t* out);
 int kad_rollout_debug_route(kad_ctx* ctx, int32_t force_width, int32_t force_long_min, int32_t force_serial);
 
+/* ------------------------------------------------------ sync dispatch planning
+ * Every reconcile of a federated object computes its placement and walks every joined cluster: is the member object
+ * created, updated, deleted, orphaned or left alone, and which propagation status does the cluster get before
+ * anything is dispatched (syncToClusters, pkg/controllers/sync/controller.go:425-544; ComputePlacement,
+ * sync/placement.go:45-116, resource.go:170-175). kad_dispatch_plan does that for a batch of objects.
+ *
+ * Cluster ids are indices into the caller's list of joined clusters, 0 .. n_clusters - 1 (at most
+ * KAD_DISPATCH_MAX_CLUSTERS; more is KAD_EUNSUPPORTED).
+ * Per cluster: cluster_flags[C]: KAD_DISPATCH_CL_READY = a Ready condition with status True
+ * (util/federatedinformer.go:292-301), _TERMINATING = a deletion timestamp is set, _CASCADING = the cascading-delete
+ * annotation is present (util/cascadingdeleteannotation.go:29-40), _FINALIZER = the cluster carries the sync
+ * controller's cascading-delete finalizer.
+ * Per object: obj_flags[O]: KAD_DISPATCH_OBJ_ERROR = the placement could not be unmarshalled: nothing is emitted and
+ * obj_result is KAD_DISPATCH_RES_PLACEMENT_FAILED; _ORPHAN_ALL / _ORPHAN_ADOPTED = GetOrphaningBehavior
+ * (util/orphaningannotation.go:48-62), never both. obj_ns[O]: >= 0 = a row of the namespace table whose placement is
+ * intersected with the object's; KAD_DISPATCH_NS_NONE = no intersection (a cluster-scoped type, or limited scope
+ * without a federated namespace); KAD_DISPATCH_NS_UNFEDERATED = a namespaced type without a federated namespace:
+ * nothing is selected (placement.go:55-64).
+ * Placement: obj_pl_off[O + 1] into pl_cluster[]: every controller's ClusterNames() in the object's own order,
+ * unsorted, duplicates allowed, -1 for a name that is not a joined cluster (dropped); the union is taken on the
+ * device. The namespace table ns_pl_off[N + 1] / ns_cluster[] follows the same rules, a row per federated namespace.
+ * Observations: obj_ob_off[O + 1] into ob_cluster[] (STRICTLY ASCENDING within an object) and ob_flags[]: an entry
+ * for every cluster where the informer holds the target (KAD_DISPATCH_OB_EXISTS, with _DELETING = it has a deletion
+ * timestamp, _ADOPTED = it carries the adopted annotation) or the lookup failed (_RETRIEVAL_FAILED); exactly one of
+ * EXISTS and RETRIEVAL_FAILED is set.
+ * out_off[O + 1] (built by the caller, from 0): object o may emit out_off[o + 1] - out_off[o] entries, which must be
+ * at least its placement entries plus its observations (a cluster neither selected nor observed never emits).
+ *
+ * Outputs: object o's entries are out_cluster / out_op (KAD_DISPATCH_OP_*) / out_status (KAD_DISPATCH_ST_*) at
+ * [out_off[o], out_off[o] + count[o]), ascending by cluster id, only clusters with an operation or a status; the
+ * slots behind them are not written. n_ops[O] = the operations started, n_selected[O] = the size of the computed
+ * placement, obj_result[O]: KAD_DISPATCH_RES_RECHECK = shouldRecheckAfterDispatch, _PLACEMENT_FAILED. The status of
+ * an entry with an operation is the one the dispatcher records when the operation is started (CreationTimedOut ...:
+ * dispatch/managed.go:330, 403, 477-481, 566-570); Wait() moves it on.
+ * The decision per (object, cluster) is csrc/kad_dispatch.h di_decide, the same function on the device and the host
+ * (kad_dispatch_decide). Declared deviation: the error branch of finalizersutil.HasFinalizer (:523-528) cannot be
+ * reached for a typed cluster object and has no input bit.
+ *
+ * Everything is validated on the host before anything is launched (KAD_EINVAL): the counts, the offsets, ids
+ * outside [-1, C) (observations: [0, C)), observations not strictly ascending, unknown or inconsistent flags,
+ * obj_ns outside [-2, N), a capacity below the bound. Runs on the ctx stream (dispatch_wave_kernel:
+ * kad_dispatch.hip); blocks until the outputs are in the caller's buffers. Needs no snapshot and reads no resident
+ * state, so a kad_group member accepts it. Leaves the last results, the timings and any later kad_schedule as they
+ * were. n_objects == 0 returns 0 without launching. */
+#define KAD_DISPATCH_MAX_CLUSTERS 16384
+#define KAD_DISPATCH_CL_READY 1u
+#define KAD_DISPATCH_CL_TERMINATING 2u
+#define KAD_DISPATCH_CL_CASCADING 4u
+#define KAD_DISPATCH_CL_FINALIZER 8u
+#define KAD_DISPATCH_OBJ_ERROR 1u
+#define KAD_DISPATCH_OBJ_ORPHAN_ALL 2u
+#define KAD_DISPATCH_OBJ_ORPHAN_ADOPTED 4u
+#define KAD_DISPATCH_OB_EXISTS 1u
+#define KAD_DISPATCH_OB_DELETING 2u
+#define KAD_DISPATCH_OB_ADOPTED 4u
+#define KAD_DISPATCH_OB_RETRIEVAL_FAILED 8u
+#define KAD_DISPATCH_NS_NONE (-1)
+#define KAD_DISPATCH_NS_UNFEDERATED (-2)
+#define KAD_DISPATCH_OP_NONE 0
+#define KAD_DISPATCH_OP_CREATE 1
+#define KAD_DISPATCH_OP_UPDATE 2
+#define KAD_DISPATCH_OP_DELETE 3
+#define KAD_DISPATCH_OP_REMOVE_LABEL 4
+#define KAD_DISPATCH_ST_NONE 0 /* never emitted */
+#define KAD_DISPATCH_ST_CLUSTER_NOT_READY 1
+#define KAD_DISPATCH_ST_CACHED_RETRIEVAL_FAILED 2
+#define KAD_DISPATCH_ST_WAITING_FOR_REMOVAL 3
+#define KAD_DISPATCH_ST_LABEL_REMOVAL_TIMED_OUT 4
+#define KAD_DISPATCH_ST_DELETION_TIMED_OUT 5
+#define KAD_DISPATCH_ST_CLUSTER_TERMINATING 6
+#define KAD_DISPATCH_ST_FINALIZER_CHECK_FAILED 7
+#define KAD_DISPATCH_ST_CREATION_TIMED_OUT 8
+#define KAD_DISPATCH_ST_UPDATE_TIMED_OUT 9
+#define KAD_DISPATCH_RES_RECHECK 1u
+#define KAD_DISPATCH_RES_PLACEMENT_FAILED 2u
+typedef struct kad_dispatch_batch {
+  int32_t n_clusters;   /* C */
+  int32_t n_objects;    /* O */
+  int32_t n_namespaces; /* N */
+  const uint8_t* cluster_flags; /* [C] KAD_DISPATCH_CL_* */
+  const uint8_t* obj_flags;     /* [O] KAD_DISPATCH_OBJ_* */
+  const int32_t* obj_ns;        /* [O] */
+  const int32_t* obj_pl_off;    /* [O + 1] */
+  const int32_t* pl_cluster;    /* [obj_pl_off[O]] */
+  const int32_t* ns_pl_off;     /* [N + 1] */
+  const int32_t* ns_cluster;    /* [ns_pl_off[N]] */
+  const int32_t* obj_ob_off;    /* [O + 1] */
+  const int32_t* ob_cluster;    /* [obj_ob_off[O]] */
+  const uint8_t* ob_flags;      /* [obj_ob_off[O]] KAD_DISPATCH_OB_* */
+  const int64_t* out_off;       /* [O + 1] */
+} kad_dispatch_batch;
+typedef struct kad_dispatch_view {
+  int32_t* out_cluster; /* [out_off[O]] */
+  uint8_t* out_op;      /* [out_off[O]] KAD_DISPATCH_OP_* */
+  uint8_t* out_status;  /* [out_off[O]] KAD_DISPATCH_ST_* */
+  int32_t* count;       /* [O] */
+  int32_t* n_ops;       /* [O] */
+  int32_t* n_selected;  /* [O] */
+  uint8_t* obj_result;  /* [O] KAD_DISPATCH_RES_* */
+} kad_dispatch_view;
+int kad_dispatch_plan(kad_ctx* ctx, const kad_dispatch_batch* batch, const kad_dispatch_view* out);
+/* Host only (no device, no ctx): the same validation; KAD_EUNSUPPORTED above KAD_DISPATCH_MAX_CLUSTERS. */
+int kad_dispatch_check(const kad_dispatch_batch* batch, const kad_dispatch_view* out);
+/* Host only: the decision for one (object, cluster) pair as the kernel takes it (csrc/kad_dispatch.h di_decide):
+ * out[0] = the operation, out[1] = the status, out[2] = 1 when the object is to be rechecked after dispatch. */
+int kad_dispatch_decide(uint32_t cluster_flags, int32_t selected, uint32_t ob_flags, uint32_t obj_flags, uint8_t out[3]);
+/* Times of the last kad_dispatch_plan that launched, from HIP events: ms[0] = the inputs' copies to the device,
+ * ms[1] = dispatch_wave_kernel, ms[2] = the outputs' copies back. */
+int kad_dispatch_timing(kad_ctx* ctx, float ms[3]);
+/* What a kad_dispatch_plan launches, as the library's one decision computes it (csrc/kad_dispatch.h route_dispatch;
+ * no device work, no ctx): out[KAD_DISPATCH_ROUTE_FIELDS] is [0] the u32 words of one bitmap = ceil(C / 32), [1]
+ * block threads, [2] blocks (one object per wave at a time, four waves a block; at most as many blocks as stay
+ * resident), [3] dynamic LDS bytes a block (three bitmaps per wave), [4] objects between two consecutive objects of
+ * one wave. kad_dispatch_last_route: the same record for the last kad_dispatch_plan that launched (KAD_ESTATE
+ * before one). */
+#define KAD_DISPATCH_ROUTE_FIELDS 5
+int kad_dispatch_route_eval(int32_t n_clusters, int32_t n_objects, int32_t n_cu, int32_t* out);
+int kad_dispatch_last_route(kad_ctx* ctx, int32_t* out);
+
 /* ------------------------------------------------ result application (§8 f3)
  * applySchedulingResult (pkg/controllers/scheduler/scheduler.go:632-695) writes a unit's result into its
  * federated object: the scheduler controller's placement (util.SetPlacementClusterNames,

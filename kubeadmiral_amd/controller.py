@@ -523,6 +523,34 @@ class BatchReconciler:
                 out[i] = o
         return out
 
+    # ------------------------------------------------------------------ sync dispatch planning
+    def reconcile_dispatch(self, objs: Sequence[dict], fed_namespaces: Optional[Dict[str, dict]], clusters: Sequence[dict],
+                           member_objs: Sequence[Dict[str, object]], finalizer: Optional[str] = None,
+                           limited_scope: bool = False) -> list:
+        """The sync controller's cluster loop for a batch of federated objects (syncToClusters,
+        pkg/controllers/sync/controller.go:425-544): ``objs[i]`` is a federated object, ``fed_namespaces`` the
+        federated namespace objects by namespace name (None: none), ``clusters`` the joined FederatedCluster objects
+        as dicts (conditions, deletion timestamp, annotations and finalizers are read) and ``member_objs[i]`` per
+        cluster name the informer's member object, None where it holds none, or the exception its lookup failed
+        with. ``finalizer``: the controller's cascading-delete finalizer (default: the one of the type config named
+        ``<plural>.<group>``). One kad_dispatch_plan answers every object (dispatch.DispatchBatch); returns per
+        object a dispatch.DispatchOutcome: the computed placement, the operation started and the propagation status
+        recorded per cluster, whether to recheck after dispatch, ComputePlacementFailed. Its ``selected`` and
+        ``rollout_members`` are what :meth:`reconcile_rollout` accepts. Objects being deleted (ensureDeletion), the
+        operations themselves, ObjectNeedsUpdate, Wait()'s status transitions and SetFederatedStatus stay with the
+        caller."""
+        from . import dispatch as DI
+
+        if finalizer is None:
+            ftc = self.type_config
+            finalizer = DI.cascading_delete_finalizer(ftc.plural_name + ("." + ftc.group if ftc.group else ""))
+        batch = DI.DispatchBatch(self.type_config, clusters, finalizer, fed_namespaces, limited_scope)
+        for fed, members in zip(objs, member_objs):
+            batch.add(fed, members)
+        if not len(batch):
+            return []
+        return batch.apply(self.ctx.dispatch_plan(**batch.arrays()))
+
     # ------------------------------------------------------------------ the reconcile over JSON texts
     def reconcile_texts(self, texts: Sequence, policies: Sequence, clusters: List[T.FederatedCluster],
                         profiles: Optional[Dict[str, Optional[dict]]] = None

@@ -1,6 +1,6 @@
 // The context behind the C ABI (include/kad_sched.h) and the host helpers every entry point shares: each
 // stage's host half (kad_api.hip, and kad_diff / kad_explain / kad_override / kad_follower / kad_migrate /
-// kad_cstat / kad_statusagg / kad_rollout / kad_trigger.hip below their kernels) includes this. The first part needs no HIP
+// kad_cstat / kad_statusagg / kad_rollout / kad_dispatch / kad_trigger.hip below their kernels) includes this. The first part needs no HIP
 // (KAD_HOST_ONLY stops there: tests/arena_main.cpp).
 #pragma once
 
@@ -78,6 +78,7 @@ inline bool csr_bad(const O* off, const int32_t* data, int64_t n, int64_t lo, in
 #include "kad_cstat.h"
 #include "kad_statusagg.h"
 #include "kad_rollout.h"
+#include "kad_dispatch.h"
 
 // A device buffer that grows on demand (grow) and frees itself: a ctx member is released by kad_ctx_destroy's
 // delete, a per-call one at the end of its scope — no list of buffers to keep.
@@ -105,7 +106,7 @@ struct Stage {
   bool ran = false;
 };
 enum StageId { STG_DIFF, STG_EXPLAIN, STG_OVERRIDE, STG_FOLLOWER, STG_MIGRATE, STG_TRIGGER, STG_CSTAT, STG_SAGG,
-               STG_ROLLOUT, STG_COUNT };
+               STG_ROLLOUT, STG_DISPATCH, STG_COUNT };
 
 struct kad_ctx {
   int device = 0;
@@ -178,6 +179,8 @@ struct kad_ctx {
   int sagg_force_width = 0, sagg_force_long_min = 0;  // kad_sagg_debug_route (0: the route's own)
   kad::RolloutRoute ro_route{};    // what the last kad_rollout_plan launched (kad_rollout_last_route)
   int ro_force_width = 0, ro_force_long_min = 0, ro_force_serial = 0;  // kad_rollout_debug_route (0: the route's own)
+  kad::DispatchRoute di_route{};   // what the last kad_dispatch_plan launched (kad_dispatch_last_route)
+  std::vector<uint8_t> di_host;    // kad_dispatch_plan: the entries as they come back, before each object's count is known
   bool group_member = false;   // owned by a kad_group: its resident results are a shard's
   // HIP event records around the stages (kad_set_timing); timed = the last
   // kad_schedule recorded them

@@ -132,6 +132,20 @@ class RolloutView(ctypes.Structure):  # kad_rollout_view
                 ("plan_flags", ctypes.c_void_p), ("action", ctypes.c_void_p), ("status", ctypes.c_void_p)]
 
 
+class DispatchBatch(ctypes.Structure):  # kad_dispatch_batch
+    _fields_ = [("n_clusters", ctypes.c_int32), ("n_objects", ctypes.c_int32), ("n_namespaces", ctypes.c_int32),
+                ("cluster_flags", ctypes.c_void_p), ("obj_flags", ctypes.c_void_p), ("obj_ns", ctypes.c_void_p),
+                ("obj_pl_off", ctypes.c_void_p), ("pl_cluster", ctypes.c_void_p), ("ns_pl_off", ctypes.c_void_p),
+                ("ns_cluster", ctypes.c_void_p), ("obj_ob_off", ctypes.c_void_p), ("ob_cluster", ctypes.c_void_p),
+                ("ob_flags", ctypes.c_void_p), ("out_off", ctypes.c_void_p)]
+
+
+class DispatchView(ctypes.Structure):  # kad_dispatch_view
+    _fields_ = [("out_cluster", ctypes.c_void_p), ("out_op", ctypes.c_void_p), ("out_status", ctypes.c_void_p),
+                ("count", ctypes.c_void_p), ("n_ops", ctypes.c_void_p), ("n_selected", ctypes.c_void_p),
+                ("obj_result", ctypes.c_void_p)]
+
+
 _lib = None
 
 
@@ -264,6 +278,13 @@ def load_library(path: str = LIB_PATH):
                                              ctypes.c_int32, P]
         L.kad_rollout_last_route.argtypes = [P, P]
         L.kad_rollout_debug_route.argtypes = [P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
+    if hasattr(L, "kad_dispatch_plan"):
+        L.kad_dispatch_plan.argtypes = [P, P, P]
+        L.kad_dispatch_check.argtypes = [P, P]
+        L.kad_dispatch_decide.argtypes = [ctypes.c_uint32, ctypes.c_int32, ctypes.c_uint32, ctypes.c_uint32, P]
+        L.kad_dispatch_timing.argtypes = [P, P]
+        L.kad_dispatch_route_eval.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, P]
+        L.kad_dispatch_last_route.argtypes = [P, P]
     L.kad_debug_inject_fault.argtypes = [P, I]
     L.kad_debug_plan_force_workspace.argtypes = [P, I]
     L.kad_trigger_suffix_upload.argtypes = [P, P, SZ]
@@ -554,6 +575,62 @@ def rollout_check(**arrays):
     nowrap = np.zeros(max(1, b.n_objects), np.uint8)
     rc = load_library().kad_rollout_check(ctypes.byref(b), ctypes.byref(v), nowrap.ctypes.data)
     return rc, nowrap[:max(0, b.n_objects)]
+
+
+DISPATCH_ROUTE = ("words", "threads", "grid", "lds", "stride")
+DISPATCH_MAX_CLUSTERS = 16384
+
+
+def dispatch_route_eval(n_clusters: int, n_objects: int, n_cu: int = 256) -> dict:
+    """kad_dispatch_route_eval: the launch decision of a dispatch_plan (needs no GPU)."""
+    out = (ctypes.c_int32 * len(DISPATCH_ROUTE))()
+    rc = load_library().kad_dispatch_route_eval(n_clusters, n_objects, n_cu, out)
+    if rc != 0:
+        raise KadError(rc, "kad_dispatch_route_eval")
+    return dict(zip(DISPATCH_ROUTE, out))
+
+
+def dispatch_decide(cluster_flags: int, selected: bool, ob_flags: int = 0, obj_flags: int = 0):
+    """kad_dispatch_decide: (op, status, recheck) of one (object, cluster) pair as the kernel decides it (no GPU)."""
+    out = (ctypes.c_uint8 * 3)()
+    rc = load_library().kad_dispatch_decide(cluster_flags, 1 if selected else 0, ob_flags, obj_flags, out)
+    if rc != 0:
+        raise KadError(rc, "kad_dispatch_decide")
+    return int(out[0]), int(out[1]), bool(out[2])
+
+
+_DISPATCH_IN = (("cluster_flags", np.uint8), ("obj_flags", np.uint8), ("obj_ns", np.int32), ("obj_pl_off", np.int32),
+                ("pl_cluster", np.int32), ("ns_pl_off", np.int32), ("ns_cluster", np.int32), ("obj_ob_off", np.int32),
+                ("ob_cluster", np.int32), ("ob_flags", np.uint8), ("out_off", np.int64))
+_DISPATCH_OUT = (("out_cluster", np.int32, 1), ("out_op", np.uint8, 1), ("out_status", np.uint8, 1),
+                 ("count", np.int32, 0), ("n_ops", np.int32, 0), ("n_selected", np.int32, 0), ("obj_result", np.uint8, 0))
+
+
+def dispatch_args(fill: int = 0, **arrays):
+    """The kad_dispatch_batch / kad_dispatch_view of one call with the arrays that back them (the batch's fields by
+    name; the counts are taken from cluster_flags, obj_flags and ns_pl_off as they are, so that a malformed batch
+    reaches the library's validation; ``n_clusters`` overrides the first). Every byte of the three entry arrays
+    starts as ``fill``. Returns (batch, view, the input arrays, the output arrays by name)."""
+    a = {k: np.ascontiguousarray(arrays[k], dt).reshape(-1) for k, dt in _DISPATCH_IN if k in arrays}
+    C = int(arrays.get("n_clusters", len(a["cluster_flags"])))
+    O, N = len(a["obj_flags"]), max(0, len(a["ns_pl_off"]) - 1)
+    oo = a["out_off"]
+    cap = int(oo[-1]) if len(oo) == O + 1 and len(oo) and 0 <= int(oo[-1]) < 2 ** 40 else 0
+    n = (O, cap)
+    out = {k: np.zeros(max(1, n[dim]), dt) for k, dt, dim in _DISPATCH_OUT}
+    if fill:
+        for k, _, dim in _DISPATCH_OUT:
+            if dim:
+                out[k].view(np.uint8)[:] = fill
+    b = DispatchBatch(C, O, N, *(a[k].ctypes.data if k in a and len(a[k]) else None for k, _ in _DISPATCH_IN))
+    v = DispatchView(*(out[k].ctypes.data for k, _, _ in _DISPATCH_OUT))
+    return b, v, a, {k: out[k][:n[dim]] for k, _, dim in _DISPATCH_OUT}
+
+
+def dispatch_check(**arrays) -> int:
+    """kad_dispatch_check: kad_dispatch_plan's validation of :func:`dispatch_args` arguments; no GPU."""
+    b, v, _keepalive, _ = dispatch_args(**arrays)
+    return load_library().kad_dispatch_check(ctypes.byref(b), ctypes.byref(v))
 
 
 class Context:
@@ -930,6 +1007,27 @@ class Context:
         """kad_rollout_debug_route: the group width / long_min of the following rollout_plan() calls (0: the
         route's own); serial = 1 walks every object serially. Measurement only."""
         self._chk(self.L.kad_rollout_debug_route(self.h, width, long_min, serial))
+
+    def dispatch_plan(self, fill: int = 0, **arrays) -> dict:
+        """kad_dispatch_plan → {out_cluster, out_op, out_status (object o's entries at out_off[o] .. + count[o]),
+        count[O], n_ops[O], n_selected[O], obj_result[O]}. Arguments as :func:`dispatch_args`
+        (dispatch.DispatchBatch.arrays()); the slots behind an object's entries keep ``fill``."""
+        b, v, _keepalive, out = dispatch_args(fill, **arrays)
+        self._chk(self.L.kad_dispatch_plan(self.h, ctypes.byref(b), ctypes.byref(v)))
+        return out
+
+    def dispatch_timing(self):
+        """kad_dispatch_timing: ms of the last dispatch_plan() — (inputs to the device, dispatch_wave_kernel,
+        outputs back)."""
+        ms = (ctypes.c_float * 3)()
+        self._chk(self.L.kad_dispatch_timing(self.h, ms))
+        return tuple(float(x) for x in ms)
+
+    def dispatch_last_route(self) -> dict:
+        """kad_dispatch_last_route: what the last dispatch_plan() launched (dispatch_route_eval's record)."""
+        out = (ctypes.c_int32 * len(DISPATCH_ROUTE))()
+        self._chk(self.L.kad_dispatch_last_route(self.h, out))
+        return dict(zip(DISPATCH_ROUTE, out))
 
     def select_rows(self, rows: Sequence[Sequence[int]], max_clusters: Sequence[Optional[int]], flags: int = 0):
         """MaxCluster on explicit score rows → per row (status, sorted selected positions)."""

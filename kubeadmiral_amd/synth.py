@@ -1539,3 +1539,49 @@ def rollout_objects(a, names):
         selected.append(set(objs))
     return feds, members, selected
 
+
+
+def gen_dispatch(seed: int, W: int, C: int, placed: int = 5, observed: float = 0.8, healthy: float = 0.9):
+    """A synthetic sync-dispatch batch as kad_dispatch_plan's arrays (the keyword arguments of
+    Context.dispatch_plan): ``W`` federated objects over ``C`` joined clusters, each placed on ``placed`` - 2 ..
+    ``placed`` + 2 clusters (uniform, as unsorted ids with the odd duplicate; 2 % of the entries name a cluster that
+    is not joined). A share ``observed`` of the objects is in its steady state — the informers hold the member
+    object in every placed cluster — the others in a uniform part of them; one object in ten is also held by a
+    cluster it has left. 3 % of the lookups failed, 5 % of the member objects are being deleted, 10 % were adopted.
+    A share ``healthy`` of the clusters is ready and carries the finalizer, the others draw the four flags at
+    random. A quarter of the objects lie in one of up to 64 federated namespaces whose placements cover 85 % of the
+    clusters, 3 % in a namespace that is not federated, 1 % have a placement that does not unmarshal; one in ten
+    orphans all, one in ten the adopted."""
+    rng = np.random.default_rng([seed, 0x6469])
+    cluster_flags = np.where(rng.random(C) < healthy, 1 | 8, rng.integers(0, 16, C)).astype(np.uint8)
+    n_pl = rng.integers(max(placed - 2, 0), placed + 3, W)
+    pl_off = np.zeros(W + 1, np.int64)
+    pl_off[1:] = np.cumsum(n_pl)
+    P = int(pl_off[-1])
+    owner = np.repeat(np.arange(W), n_pl)
+    pl_cluster = rng.integers(0, C, P)
+    rank = np.arange(P) - pl_off[owner]
+    held = np.where(rng.random(W) < observed, n_pl, (rng.random(W) * (n_pl + 1)).astype(np.int64))
+    pl_cluster = np.where(rng.random(P) < 0.02, -1, pl_cluster)
+    seen = (rank < held[owner]) & (pl_cluster >= 0)
+    stray = np.flatnonzero(rng.random(W) < 0.1)
+    keys = np.unique(np.concatenate((owner[seen] * C + pl_cluster[seen], stray * C + rng.integers(0, C, len(stray)))))
+    ob_owner, ob_cluster = keys // C, keys % C
+    B = len(keys)
+    u = rng.random(B)
+    ob_flags = np.where(u < 0.03, 8, np.where(u < 0.08, 1 | 2, np.where(u < 0.18, 1 | 4, 1))).astype(np.uint8)
+    ob_off = np.zeros(W + 1, np.int64)
+    ob_off[1:] = np.cumsum(np.bincount(ob_owner, minlength=W))
+    N = max(1, min(64, W // 8))
+    rows = [np.where(rng.random(C) < 0.02, -1, rng.permutation(C))[:max(1, int(C * 0.85))] for _ in range(N)]
+    ns_off = np.zeros(N + 1, np.int64)
+    ns_off[1:] = np.cumsum([len(r) for r in rows])
+    u = rng.random(W)
+    obj_ns = np.where(u < 0.25, rng.integers(0, N, W), np.where(u < 0.28, -2, -1))
+    u = rng.random(W)
+    obj_flags = (np.where(u < 0.1, 2, np.where(u < 0.2, 4, 0)) | (rng.random(W) < 0.01)).astype(np.uint8)
+    return dict(cluster_flags=cluster_flags, obj_flags=obj_flags, obj_ns=obj_ns.astype(np.int32),
+                obj_pl_off=pl_off.astype(np.int32), pl_cluster=pl_cluster.astype(np.int32),
+                ns_pl_off=ns_off.astype(np.int32), ns_cluster=np.concatenate(rows).astype(np.int32),
+                obj_ob_off=ob_off.astype(np.int32), ob_cluster=ob_cluster.astype(np.int32), ob_flags=ob_flags,
+                out_off=pl_off + ob_off)
