@@ -1389,9 +1389,16 @@ int kad_select_rows(kad_ctx* c, int n_rows, const int32_t* row_off, const int64_
       if (k > 65535) return fail(c, KAD_EINVAL, "row longer than 65535");
       kmax = k > kmax ? k : kmax;
     }
+    const int32_t* d_off;
+    const int64_t *d_sc, *d_mc;
+    int32_t *d_cnt, *d_sel, *d_st;
     Arena a;
-    const Part p_off = a.in(row_off, 4 * (n + 1)), p_sc = a.in(scores, 8 * tot), p_mc = a.in(maxc, 8 * n),
-               o_cnt = a.out(4 * n), o_sel = a.out(4 * tot), o_st = a.out(4 * n);
+    a.in(d_off, row_off, n + 1);
+    a.in(d_sc, scores, tot);
+    a.in(d_mc, maxc, n);
+    a.out(d_cnt, out_count, n);
+    a.out(d_sel, out_sel, tot);
+    a.out(d_st, out_status, n);
     DevBuf buf, scr;  // per call: freed on every way out
     if (int r = a.commit(c, buf)) return r;
     const size_t wb = select_wave_bytes(kmax);
@@ -1399,14 +1406,9 @@ int kad_select_rows(kad_ctx* c, int n_rows, const int32_t* row_off, const int64_
       scr.cap = wb * (size_t)(n_rows < 4096 ? n_rows : 4096);
       HIPCHK(c, hipMalloc(&scr.p, scr.cap));
     }
-    int32_t *d_cnt = a.ptr<int32_t>(buf, o_cnt), *d_sel = a.ptr<int32_t>(buf, o_sel), *d_st = a.ptr<int32_t>(buf, o_st);
-    hipError_t e = launch_select_rows(n_rows, a.ptr<const int32_t>(buf, p_off), a.ptr<const int64_t>(buf, p_sc),
-                                      a.ptr<const int64_t>(buf, p_mc), pflags, kmax, d_cnt, d_sel, d_st, scr.p, scr.cap,
-                                      c->stream);
+    hipError_t e = launch_select_rows(n_rows, d_off, d_sc, d_mc, pflags, kmax, d_cnt, d_sel, d_st, scr.p, scr.cap, c->stream);
     if (e == hipSuccess) {
-      (void)hipMemcpyAsync(out_count, d_cnt, n * 4, hipMemcpyDeviceToHost, c->stream);
-      if (tot) (void)hipMemcpyAsync(out_sel, d_sel, tot * 4, hipMemcpyDeviceToHost, c->stream);
-      (void)hipMemcpyAsync(out_status, d_st, n * 4, hipMemcpyDeviceToHost, c->stream);
+      (void)a.fetch(c);  // a failed copy shows at the synchronisation
       e = hipStreamSynchronize(c->stream);
     }
     if (e != hipSuccess) return fail(c, KAD_EHIP, hipGetErrorString(e));
@@ -1426,27 +1428,23 @@ int kad_plan_rows(kad_ctx* c, int n_rows, const int32_t* row_off, const uint32_t
       const int k = row_off[r + 1] - row_off[r];
       kmax = k > kmax ? k : kmax;
     }
-    Arena a;
-    const Part p_off = a.in(row_off, 4 * (n + 1)), p_hash = a.in(hash, 4 * tot), p_w = a.in(weight, 8 * tot),
-               p_mn = a.in(min_r, 8 * tot), p_mx = a.in(max_r, 8 * tot), p_cap = a.in(cap, 8 * tot),
-               p_cur = a.in(current, 8 * tot), p_ef = a.in(elem_flags, 4 * tot), p_tot = a.in(total, 8 * n),
-               p_rf = a.in(row_flags, 4 * n), o_plan = a.out(8 * tot), o_over = a.out(8 * tot);
-    DevBuf buf, scr;  // per call: freed on every way out
-    if (int r = a.commit(c, buf)) return r;
     PlanRowsDev R{};
     R.n_rows = n_rows;
-    R.row_off = a.ptr<const int32_t>(buf, p_off);
-    R.hash = a.ptr<const uint32_t>(buf, p_hash);
-    R.weight = a.ptr<const int64_t>(buf, p_w);
-    R.min_r = a.ptr<const int64_t>(buf, p_mn);
-    R.max_r = a.ptr<const int64_t>(buf, p_mx);
-    R.cap = a.ptr<const int64_t>(buf, p_cap);
-    R.current = a.ptr<const int64_t>(buf, p_cur);
-    R.elem_flags = a.ptr<const uint32_t>(buf, p_ef);
-    R.total = a.ptr<const int64_t>(buf, p_tot);
-    R.row_flags = a.ptr<const uint32_t>(buf, p_rf);
-    R.out_plan = a.ptr<int64_t>(buf, o_plan);
-    R.out_overflow = a.ptr<int64_t>(buf, o_over);
+    Arena a;
+    a.in(R.row_off, row_off, n + 1);
+    a.in(R.hash, hash, tot);
+    a.in(R.weight, weight, tot);
+    a.in(R.min_r, min_r, tot);
+    a.in(R.max_r, max_r, tot);
+    a.in(R.cap, cap, tot);
+    a.in(R.current, current, tot);
+    a.in(R.elem_flags, elem_flags, tot);
+    a.in(R.total, total, n);
+    a.in(R.row_flags, row_flags, n);
+    a.out(R.out_plan, out_plan, tot);
+    a.out(R.out_overflow, out_overflow, tot);
+    DevBuf buf, scr;  // per call: freed on every way out
+    if (int r = a.commit(c, buf)) return r;
     const size_t wb = plan_wave_bytes(kmax);
     if (wb > 64 * 1024) {
       scr.cap = wb * (size_t)(n_rows < 4096 ? n_rows : 4096);
@@ -1454,10 +1452,7 @@ int kad_plan_rows(kad_ctx* c, int n_rows, const int32_t* row_off, const uint32_t
     }
     hipError_t e = launch_plan_rows(R, kmax, c->plan_force_ws, scr.p, scr.cap, c->stream);
     if (e == hipSuccess) {
-      if (tot) {
-        (void)hipMemcpyAsync(out_plan, R.out_plan, tot * 8, hipMemcpyDeviceToHost, c->stream);
-        (void)hipMemcpyAsync(out_overflow, R.out_overflow, tot * 8, hipMemcpyDeviceToHost, c->stream);
-      }
+      (void)a.fetch(c);  // a failed copy shows at the synchronisation
       e = hipStreamSynchronize(c->stream);
     }
     if (e != hipSuccess) return fail(c, KAD_EHIP, hipGetErrorString(e));

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "kad_groups.h"
+
 namespace kad {
 
 constexpr int CS_MAX_RES = 64;         // resource names of a call: one presence bit each
@@ -62,30 +64,16 @@ struct CstatRoute {
   int32_t chunk_grid;   // blocks of the pod pass's long path = n_chunks
 };
 
-inline int cs_width(int64_t items, int64_t rows) {
-  const int64_t mean = rows > 0 ? (items + rows - 1) / rows : 0;
-  const int64_t want = (mean + 7) / 8;
-  int w = CS_MIN_WIDTH;
-  while (w < 64 && w < want) w <<= 1;
-  return w;
-}
-
-inline int32_t cs_grid(int64_t rows, int width, int n_cu) {
-  // at most 16.5 KiB of LDS a block: 8 blocks (32 waves) a CU, each lane group striding
-  const int64_t per_block = 256 / width, want = (rows + per_block - 1) / per_block, cap = (int64_t)n_cu * 8;
-  return (int32_t)(want < cap ? want : cap);
-}
-
 inline CstatRoute route_cstat(int K, int n_long, int64_t short_nodes, int64_t short_pods, int n_chunks, int n_cu) {
   CstatRoute r{};
   const int n_short = K - n_long;
-  r.node_width = cs_width(short_nodes, n_short);
-  r.pod_width = cs_width(short_pods, n_short);
+  r.node_width = group_width(short_nodes, n_short, CS_MIN_WIDTH, 8);
+  r.pod_width = group_width(short_pods, n_short, CS_MIN_WIDTH, 8);
   r.long_min = CS_LONG_MIN;
   r.threads = 256;
-  // the groups stride over all K clusters and skip the long ones
-  r.node_grid = n_short > 0 ? cs_grid(K, r.node_width, n_cu) : 0;
-  r.pod_grid = n_short > 0 ? cs_grid(K, r.pod_width, n_cu) : 0;
+  // the groups stride over all K clusters and skip the long ones; at most 16.5 KiB of LDS a block
+  r.node_grid = n_short > 0 ? group_grid(K, r.node_width, n_cu) : 0;
+  r.pod_grid = n_short > 0 ? group_grid(K, r.pod_width, n_cu) : 0;
   r.long_grid = n_long;
   r.chunk_grid = n_chunks;
   return r;

@@ -187,28 +187,20 @@ __global__ __launch_bounds__(256) void cstat_combine_kernel(CstatDev d) {
 hipError_t launch_cstat_nodes(const CstatDev& d, const CstatRoute& r, hipStream_t st) {
   (void)hipGetLastError();
   const unsigned grid = (unsigned)(r.node_grid + r.long_grid);
-  if (grid > 0) {
-    switch (r.node_width) {
-      case 8: hipLaunchKernelGGL(cstat_node_kernel<8>, dim3(grid), dim3(256), 0, st, d); break;
-      case 16: hipLaunchKernelGGL(cstat_node_kernel<16>, dim3(grid), dim3(256), 0, st, d); break;
-      case 32: hipLaunchKernelGGL(cstat_node_kernel<32>, dim3(grid), dim3(256), 0, st, d); break;
-      default: hipLaunchKernelGGL(cstat_node_kernel<64>, dim3(grid), dim3(256), 0, st, d); break;
-    }
-  }
+  if (grid > 0)
+    with_width<CS_MIN_WIDTH>(r.node_width, [&](auto W) {
+      hipLaunchKernelGGL(cstat_node_kernel<decltype(W)::value>, dim3(grid), dim3(256), 0, st, d);
+    });
   return hipGetLastError();
 }
 
 hipError_t launch_cstat_pods(const CstatDev& d, const CstatRoute& r, hipStream_t st) {
   (void)hipGetLastError();
   const unsigned grid = (unsigned)(r.pod_grid + r.chunk_grid);
-  if (grid > 0) {
-    switch (r.pod_width) {
-      case 8: hipLaunchKernelGGL(cstat_pod_kernel<8>, dim3(grid), dim3(256), 0, st, d); break;
-      case 16: hipLaunchKernelGGL(cstat_pod_kernel<16>, dim3(grid), dim3(256), 0, st, d); break;
-      case 32: hipLaunchKernelGGL(cstat_pod_kernel<32>, dim3(grid), dim3(256), 0, st, d); break;
-      default: hipLaunchKernelGGL(cstat_pod_kernel<64>, dim3(grid), dim3(256), 0, st, d); break;
-    }
-  }
+  if (grid > 0)
+    with_width<CS_MIN_WIDTH>(r.pod_width, [&](auto W) {
+      hipLaunchKernelGGL(cstat_pod_kernel<decltype(W)::value>, dim3(grid), dim3(256), 0, st, d);
+    });
   const int64_t n = (int64_t)d.n_long * d.R;
   if (n > 0) hipLaunchKernelGGL(cstat_combine_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d);
   return hipGetLastError();
@@ -328,7 +320,8 @@ static int validate_cstat(const kad_cstat_batch* b, const kad_cstat_view* out, i
 }
 
 static int cluster_resources_locked(kad_ctx* c, const kad_cstat_batch* b, const kad_cstat_view* out) {
-  const int long_min = c->cs_force_long_min > 0 ? c->cs_force_long_min : CS_LONG_MIN;
+  Stage& stg = c->stage[STG_CSTAT];
+  const int long_min = stg.force.long_min_or(CS_LONG_MIN);
   std::string err;
   CstatPlan plan;
   if (int r = validate_cstat(b, out, long_min, &plan, &err)) return fail(c, r, err);
@@ -337,76 +330,58 @@ static int cluster_resources_locked(kad_ctx* c, const kad_cstat_batch* b, const 
   HIPCHK(c, hipSetDevice(c->device));
   const int n_long = (int)plan.long_list.size(), n_chunks = (int)plan.chunk_cluster.size();
   CstatRoute route = route_cstat(K, n_long, plan.short_nodes, plan.short_pods, n_chunks, n_cus());
-  if (c->cs_force_width > 0 && n_long < K) {
-    route.node_width = route.pod_width = c->cs_force_width;
-    route.node_grid = route.pod_grid = cs_grid(K, c->cs_force_width, n_cus());
-  }
+  group_force_apply(stg.force, n_long < K, K, n_cus(), route.node_width, route.node_grid);
+  group_force_apply(stg.force, n_long < K, K, n_cus(), route.pod_width, route.pod_grid);
   route.long_min = long_min;
   // one buffer: the inputs, then the partial sums and the outputs
   const size_t k = (size_t)K, n = (size_t)b->n_nodes, p = (size_t)b->n_pods, en = (size_t)b->n_node_ents,
                ep = (size_t)b->n_pod_ents, nl = (size_t)n_long, nc = (size_t)n_chunks, kr = k * (size_t)R;
-  Arena a;
-  const Part p_cn = a.in(b->cl_node_off, 8 * (k + 1)), p_nf = a.in(b->node_flags, n), p_ne = a.in(b->node_ent_off, 8 * (n + 1)),
-             p_nr = a.in(b->nent_res, en), p_nv = a.in(b->nent_val, 8 * en), p_cp = a.in(b->cl_pod_off, 8 * (k + 1)),
-             p_pf = a.in(b->pod_flags, p), p_pe = a.in(b->pod_ent_off, 8 * (p + 1)), p_pr = a.in(b->pent_res, ep),
-             p_pk = a.in(b->pent_kind, ep), p_pv = a.in(b->pent_val, 8 * ep), p_cl = a.in(plan.cl_long.data(), k),
-             p_ll = a.in(plan.long_list.data(), 4 * nl), p_lc = a.in(plan.long_chunk_off.data(), 4 * (nl + 1)),
-             p_cc = a.in(plan.chunk_cluster.data(), 4 * nc), p_lo = a.in(plan.chunk_lo.data(), 8 * nc),
-             p_hi = a.in(plan.chunk_hi.data(), 8 * nc);
-  const Part o_part = a.out(8 * nc * (size_t)R), o_alloc = a.out(8 * kr), o_avail = a.out(8 * kr), o_has = a.out(8 * k),
-             o_sn = a.out(8 * k);
-  Stage& stg = c->stage[STG_CSTAT];
-  if (int r = a.commit(c, stg.buf)) return r;
   CstatDev d{};
   d.K = K;
   d.R = R;
   d.n_long = n_long;
   d.n_chunks = n_chunks;
-  d.cl_node_off = a.ptr<const int64_t>(stg.buf, p_cn);
-  d.node_flags = a.ptr<const uint8_t>(stg.buf, p_nf);
-  d.node_ent_off = a.ptr<const int64_t>(stg.buf, p_ne);
-  d.nent_res = a.ptr<const uint8_t>(stg.buf, p_nr);
-  d.nent_val = a.ptr<const int64_t>(stg.buf, p_nv);
-  d.cl_pod_off = a.ptr<const int64_t>(stg.buf, p_cp);
-  d.pod_flags = a.ptr<const uint8_t>(stg.buf, p_pf);
-  d.pod_ent_off = a.ptr<const int64_t>(stg.buf, p_pe);
-  d.pent_res = a.ptr<const uint8_t>(stg.buf, p_pr);
-  d.pent_kind = a.ptr<const uint8_t>(stg.buf, p_pk);
-  d.pent_val = a.ptr<const int64_t>(stg.buf, p_pv);
-  d.cl_long = a.ptr<const uint8_t>(stg.buf, p_cl);
-  d.long_list = a.ptr<const int32_t>(stg.buf, p_ll);
-  d.long_chunk_off = a.ptr<const int32_t>(stg.buf, p_lc);
-  d.chunk_cluster = a.ptr<const int32_t>(stg.buf, p_cc);
-  d.chunk_pod_lo = a.ptr<const int64_t>(stg.buf, p_lo);
-  d.chunk_pod_hi = a.ptr<const int64_t>(stg.buf, p_hi);
-  d.partial = a.ptr<uint64_t>(stg.buf, o_part);
-  d.alloc = a.ptr<int64_t>(stg.buf, o_alloc);
-  d.avail = a.ptr<int64_t>(stg.buf, o_avail);
-  d.has = a.ptr<uint64_t>(stg.buf, o_has);
-  d.sched_nodes = a.ptr<int64_t>(stg.buf, o_sn);
+  Arena a;
+  a.in(d.cl_node_off, b->cl_node_off, k + 1);
+  a.in(d.node_flags, b->node_flags, n);
+  a.in(d.node_ent_off, b->node_ent_off, n + 1);
+  a.in(d.nent_res, b->nent_res, en);
+  a.in(d.nent_val, b->nent_val, en);
+  a.in(d.cl_pod_off, b->cl_pod_off, k + 1);
+  a.in(d.pod_flags, b->pod_flags, p);
+  a.in(d.pod_ent_off, b->pod_ent_off, p + 1);
+  a.in(d.pent_res, b->pent_res, ep);
+  a.in(d.pent_kind, b->pent_kind, ep);
+  a.in(d.pent_val, b->pent_val, ep);
+  a.in(d.cl_long, plan.cl_long.data(), k);
+  a.in(d.long_list, plan.long_list.data(), nl);
+  a.in(d.long_chunk_off, plan.long_chunk_off.data(), nl + 1);
+  a.in(d.chunk_cluster, plan.chunk_cluster.data(), nc);
+  a.in(d.chunk_pod_lo, plan.chunk_lo.data(), nc);
+  a.in(d.chunk_pod_hi, plan.chunk_hi.data(), nc);
+  a.out(d.partial, nc * (size_t)R);
+  a.out(d.alloc, out->alloc, kr);
+  a.out(d.avail, out->avail, kr);
+  a.out(d.has, out->has, k);
+  a.out(d.sched_nodes, out->sched_nodes, k);
+  if (int r = a.commit(c, stg.buf)) return r;
   HIPCHK(c, hipEventRecord(stg.ev[0], c->stream));
   HIPCHK(c, launch_cstat_nodes(d, route, c->stream));
   HIPCHK(c, hipEventRecord(stg.ev[1], c->stream));
   HIPCHK(c, launch_cstat_pods(d, route, c->stream));
   HIPCHK(c, hipEventRecord(stg.ev[2], c->stream));
-  stg.ran = true;
-  c->cs_route = route;
-  HIPCHK(c, hipMemcpyAsync(out->alloc, d.alloc, 8 * kr, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(out->avail, d.avail, 8 * kr, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(out->has, d.has, 8 * k, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(out->sched_nodes, d.sched_nodes, 8 * k, hipMemcpyDeviceToHost, c->stream));
+  stage_ran(stg, route);
+  if (int r = a.fetch(c)) return r;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return KAD_OK;
 }
 
 int kad_cstat_check(const kad_cstat_batch* b, const kad_cstat_view* out) {
-  try {
+  return check_guarded([&]() -> int {
     if (!b) return KAD_EINVAL;
     std::string err;
     return validate_cstat(b, out, CS_LONG_MIN, nullptr, &err);
-  } catch (...) {
-    return KAD_EHOST;
-  }
+  });
 }
 
 int kad_cluster_resources(kad_ctx* c, const kad_cstat_batch* b, const kad_cstat_view* out) {
@@ -415,36 +390,20 @@ int kad_cluster_resources(kad_ctx* c, const kad_cstat_batch* b, const kad_cstat_
   });
 }
 
-int kad_cstat_timing(kad_ctx* c, float ms[2]) {
-  return entry(c, ms != nullptr, [&] { return stage_timing(c, c->stage[STG_CSTAT], 2, ms, "no kad_cluster_resources ran"); });
-}
+int kad_cstat_timing(kad_ctx* c, float ms[2]) { return stage_timing(c, STG_CSTAT, 2, ms, "no kad_cluster_resources ran"); }
 
 int kad_cstat_route_eval(int32_t n_clusters, int32_t n_long, int64_t short_nodes, int64_t short_pods, int32_t n_chunks,
                          int32_t n_cu, int32_t* out) {
   if (!out || n_clusters < 0 || n_long < 0 || n_long > n_clusters || short_nodes < 0 || short_pods < 0 || n_chunks < 0 ||
       n_cu < 1)
     return KAD_EINVAL;
-  const CstatRoute r = route_cstat(n_clusters, n_long, short_nodes, short_pods, n_chunks, n_cu);
-  static_assert(sizeof r == 4 * KAD_CS_ROUTE_FIELDS, "kad_cstat_route_eval's record");
-  memcpy(out, &r, sizeof r);
-  return KAD_OK;
+  return route_record<KAD_CS_ROUTE_FIELDS>(out, route_cstat(n_clusters, n_long, short_nodes, short_pods, n_chunks, n_cu));
 }
 
-int kad_cstat_last_route(kad_ctx* c, int32_t* out) {
-  return entry(c, out != nullptr, [&]() -> int {
-    if (!c->stage[STG_CSTAT].ran) return fail(c, KAD_ESTATE, "no kad_cluster_resources ran");
-    memcpy(out, &c->cs_route, sizeof c->cs_route);
-    return KAD_OK;
-  });
-}
+int kad_cstat_last_route(kad_ctx* c, int32_t* out) { return stage_last_route(c, STG_CSTAT, out, "no kad_cluster_resources ran"); }
 
 int kad_cstat_debug_route(kad_ctx* c, int32_t force_width, int32_t force_long_min) {
-  const bool width_ok = force_width == 0 || force_width == 8 || force_width == 16 || force_width == 32 || force_width == 64;
-  return entry(c, force_long_min >= 0 && width_ok, [&]() -> int {
-    c->cs_force_width = force_width;
-    c->cs_force_long_min = force_long_min;
-    return KAD_OK;
-  });
+  return stage_debug_route(c, STG_CSTAT, group_width_ok(force_width, CS_MIN_WIDTH), GroupForce{force_width, force_long_min, 0});
 }
 
 }  // extern "C"

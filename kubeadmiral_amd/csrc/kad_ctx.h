@@ -1,7 +1,6 @@
 // The context behind the C ABI (include/kad_sched.h) and the host helpers every entry point shares: each
-// stage's host half (kad_api.hip, and kad_diff / kad_explain / kad_override / kad_follower / kad_migrate /
-// kad_cstat / kad_statusagg / kad_rollout / kad_dispatch / kad_trigger.hip below their kernels) includes this. The first part needs no HIP
-// (KAD_HOST_ONLY stops there: tests/arena_main.cpp).
+// stage's host half (kad_api.hip, and every consumer's .hip below its kernels) includes this; it includes no
+// consumer's header. The first part needs no HIP (KAD_HOST_ONLY stops there: tests/arena_main.cpp).
 #pragma once
 
 #include <atomic>
@@ -73,12 +72,7 @@ inline bool csr_bad(const O* off, const int32_t* data, int64_t n, int64_t lo, in
 
 #include "../../include/kad_sched.h"
 #include "kad_device.h"
-#include "kad_follower.h"
-#include "kad_migrate.h"
-#include "kad_cstat.h"
-#include "kad_statusagg.h"
-#include "kad_rollout.h"
-#include "kad_dispatch.h"
+#include "kad_groups.h"
 
 // A device buffer that grows on demand (grow) and frees itself: a ctx member is released by kad_ctx_destroy's
 // delete, a per-call one at the end of its scope — no list of buffers to keep.
@@ -99,11 +93,16 @@ struct DevBuf {
 };
 
 // One consumer of the scheduler's results: its staging buffer (kad_arena.h), the events
-// recorded around its kernels (ev[0] the start) and whether they hold a run (stage_timing).
+// recorded around its kernels (ev[0] the start), whether they hold a run (stage_timing), what that run launched
+// (the call's route record as it stands in include/kad_sched.h: stage_ran / stage_last_route) and what its
+// kad_*_debug_route forces on the next ones.
 struct Stage {
   DevBuf buf;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   bool ran = false;
+  int32_t route[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  int route_n = 0;  // fields of `route` in use
+  kad::GroupForce force;
 };
 enum StageId { STG_DIFF, STG_EXPLAIN, STG_OVERRIDE, STG_FOLLOWER, STG_MIGRATE, STG_TRIGGER, STG_CSTAT, STG_SAGG,
                STG_ROLLOUT, STG_DISPATCH, STG_COUNT };
@@ -155,9 +154,8 @@ struct kad_ctx {
   int64_t unit_lo = 0, unit_n = 0, slot_lo = 0, slot_n = 0;
   int inject_fault = 0;  // kad_debug_inject_fault: 1 = the next refresh_derived fails (tests)
   int plan_force_ws = 0;  // kad_debug_plan_force_workspace: kad_plan_rows through the workspace planner (tests)
-  // the consumers of the results: kad_result_diff (canonical object state + flags), kad_explain (unit list,
-  // then the outputs), kad_override_match, kad_follower_union, kad_migrate_estimate (one call's inputs and
-  // outputs each) and the trigger hashes (prefix_off, out)
+  // the consumers of the results, one Stage each (StageId): a call's inputs and outputs in its buffer, its
+  // last route and forced route beside them
   Stage stage[STG_COUNT];
   // override policies (kad_override_*): the resident policy-set blob, its requirement routing (the layout of
   // h_reqseg) and its rows (requirement rows [NR][nch], then M and E [R][nch] each)
@@ -170,16 +168,6 @@ struct kad_ctx {
   int ovr_n_seg = 0, ovr_n_rowreq = 0, ovr_n_seg_reqs = 0;
   DevBuf d_ovr_rows;
   int32_t cur_lo = 0, cur_n = 0;  // the resident batch's (shard's) range of KAD_B_CUR_ID entries
-  kad::FollowerRoute fol_route{};  // what the last kad_follower_union launched (kad_follower_last_route)
-  kad::MigrateRoute mig_route{};   // what the last kad_migrate_estimate launched (kad_migrate_last_route)
-  int mig_force_width = 0, mig_force_long_min = 0;  // kad_migrate_debug_route (0: the route's own)
-  kad::CstatRoute cs_route{};      // what the last kad_cluster_resources launched (kad_cstat_last_route)
-  int cs_force_width = 0, cs_force_long_min = 0;    // kad_cstat_debug_route (0: the route's own)
-  kad::SaggRoute sagg_route{};     // what the last kad_status_aggregate launched (kad_sagg_last_route)
-  int sagg_force_width = 0, sagg_force_long_min = 0;  // kad_sagg_debug_route (0: the route's own)
-  kad::RolloutRoute ro_route{};    // what the last kad_rollout_plan launched (kad_rollout_last_route)
-  int ro_force_width = 0, ro_force_long_min = 0, ro_force_serial = 0;  // kad_rollout_debug_route (0: the route's own)
-  kad::DispatchRoute di_route{};   // what the last kad_dispatch_plan launched (kad_dispatch_last_route)
   std::vector<uint8_t> di_host;    // kad_dispatch_plan: the entries as they come back, before each object's count is known
   bool group_member = false;   // owned by a kad_group: its resident results are a shard's
   // HIP event records around the stages (kad_set_timing); timed = the last
@@ -257,13 +245,55 @@ inline int grow(kad_ctx* c, DevBuf& b, size_t need) {
   return 0;
 }
 
+// ---- the ABI glue of a consumer call: kad_*_timing, kad_*_route_eval, kad_*_last_route, kad_*_debug_route and
+// kad_*_check are one line each over these
 // ms[i] = the time between a stage's events i and i + 1, for its n intervals; KAD_ESTATE (none_ran) before
 // its first run
-inline int stage_timing(kad_ctx* c, const Stage& s, int n, float* ms, const char* none_ran) {
-  if (!s.ran) return fail(c, KAD_ESTATE, none_ran);
-  HIPCHK(c, hipEventSynchronize(s.ev[n]));
-  for (int i = 0; i < n; i++) HIPCHK(c, hipEventElapsedTime(&ms[i], s.ev[i], s.ev[i + 1]));
+inline int stage_timing(kad_ctx* c, StageId id, int n, float* ms, const char* none_ran) {
+  return entry(c, ms != nullptr, [&]() -> int {
+    const Stage& s = c->stage[id];
+    if (!s.ran) return fail(c, KAD_ESTATE, none_ran);
+    HIPCHK(c, hipEventSynchronize(s.ev[n]));
+    for (int i = 0; i < n; i++) HIPCHK(c, hipEventElapsedTime(&ms[i], s.ev[i], s.ev[i + 1]));
+    return KAD_OK;
+  });
+}
+// a route struct as the FIELDS int32_t of its record in include/kad_sched.h
+template <int FIELDS, class R>
+inline int route_record(int32_t* out, const R& r) {
+  static_assert(sizeof(R) == 4 * FIELDS && FIELDS <= 8, "a route record: the struct's int32_t fields, 8 at most");
+  memcpy(out, &r, sizeof r);
   return KAD_OK;
+}
+// the stage's events hold a run that launched r
+template <class R>
+inline void stage_ran(Stage& s, const R& r) {
+  s.ran = true;
+  s.route_n = (int)(sizeof(R) / 4);
+  route_record<sizeof(R) / 4>(s.route, r);
+}
+inline int stage_last_route(kad_ctx* c, StageId id, int32_t* out, const char* none_ran) {
+  return entry(c, out != nullptr, [&]() -> int {
+    const Stage& s = c->stage[id];
+    if (!s.ran) return fail(c, KAD_ESTATE, none_ran);
+    memcpy(out, s.route, 4 * (size_t)s.route_n);
+    return KAD_OK;
+  });
+}
+inline int stage_debug_route(kad_ctx* c, StageId id, bool args_ok, const kad::GroupForce& f) {
+  return entry(c, args_ok && f.long_min >= 0, [&]() -> int {
+    c->stage[id].force = f;
+    return KAD_OK;
+  });
+}
+// a host-only kad_*_check: nothing unwinds through the C ABI, and there is no ctx to keep a message
+template <class F>
+inline int check_guarded(F f) {
+  try {
+    return f();
+  } catch (...) {
+    return KAD_EHOST;
+  }
 }
 
 inline kad::OutDev out_dev(kad_ctx* c) {

@@ -124,14 +124,6 @@ int kad_result_diff(kad_ctx* c, const kad_result_state* st, uint32_t* out) {
     // one device buffer: [pl_off | pl_id | ov_off | ov_id | ov_val | uflag | ov_kind | out]; the kernel may read
     // one element past pl_id, ov_id, ov_val and ov_kind
     const size_t w = (size_t)W, no = (size_t)NO;
-    Arena a;
-    const Part p_ploff = a.in(pl_off.data(), 4 * (w + 1)), p_plid = a.in(pl_id.data(), 4 * (size_t)pl_off[W], 4),
-               p_ovoff = a.in(st->ovr_off, 4 * (w + 1)), p_ovid = a.in(st->ovr_cluster, 4 * no, 4),
-               p_ovval = a.in(st->ovr_value, 8 * no, 8), p_uf = a.in(uflag.data(), w), p_ovk = a.in(st->ovr_kind, no, 1),
-               o_out = a.out(4 * w);
-    HIPCHK(c, hipSetDevice(c->device));
-    DevBuf& buf = c->stage[STG_DIFF].buf;
-    if (int r = a.commit(c, buf)) return r;
     ResultDiffDev dd{};
     dd.W = W;
     dd.status = c->d_status;
@@ -140,16 +132,19 @@ int kad_result_diff(kad_ctx* c, const kad_result_state* st, uint32_t* out) {
     dd.cluster = od.cluster;
     dd.replicas = od.replicas;
     dd.out_off = c->bd.out_off;
-    dd.pl_off = a.ptr<const int32_t>(buf, p_ploff);
-    dd.pl_id = a.ptr<const int32_t>(buf, p_plid);
-    dd.uflag = a.ptr<const uint8_t>(buf, p_uf);
-    dd.ov_off = a.ptr<const int32_t>(buf, p_ovoff);
-    dd.ov_id = a.ptr<const int32_t>(buf, p_ovid);
-    dd.ov_val = a.ptr<const int64_t>(buf, p_ovval);
-    dd.ov_kind = a.ptr<const uint8_t>(buf, p_ovk);
-    dd.out = a.ptr<uint32_t>(buf, o_out);
+    Arena a;
+    a.in(dd.pl_off, pl_off.data(), w + 1);
+    a.in(dd.pl_id, pl_id.data(), (size_t)pl_off[W], 1);
+    a.in(dd.ov_off, st->ovr_off, w + 1);
+    a.in(dd.ov_id, st->ovr_cluster, no, 1);
+    a.in(dd.ov_val, st->ovr_value, no, 1);
+    a.in(dd.uflag, uflag.data(), w);
+    a.in(dd.ov_kind, st->ovr_kind, no, 1);
+    a.out(dd.out, out, w);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int r = a.commit(c, c->stage[STG_DIFF].buf)) return r;
     HIPCHK(c, launch_result_diff(dd, c->stream));
-    HIPCHK(c, hipMemcpyAsync(out, dd.out, 4 * w, hipMemcpyDeviceToHost, c->stream));
+    if (int r = a.fetch(c)) return r;
     HIPCHK(c, hipStreamSynchronize(c->stream));  // the caller's state arrays are free on return
     return KAD_OK;
   });

@@ -219,59 +219,50 @@ static int dispatch_plan_locked(kad_ctx* c, const kad_dispatch_batch* b, const k
   const size_t o = (size_t)O, n = (size_t)N, np = (size_t)b->obj_pl_off[O], nn = (size_t)b->ns_pl_off[N],
                nb = (size_t)b->obj_ob_off[O], cap = (size_t)b->out_off[O];
   Stage& stg = c->stage[STG_DISPATCH];
-  Arena a;
-  const Part p_cf = a.in(b->cluster_flags, (size_t)C), p_of = a.in(b->obj_flags, o), p_ns = a.in(b->obj_ns, 4 * o),
-             p_po = a.in(b->obj_pl_off, 4 * (o + 1)), p_pc = a.in(b->pl_cluster, 4 * np),
-             p_no = a.in(b->ns_pl_off, 4 * (n + 1)), p_nc = a.in(b->ns_cluster, 4 * nn),
-             p_oo = a.in(b->obj_ob_off, 4 * (o + 1)), p_oc = a.in(b->ob_cluster, 4 * nb), p_ob = a.in(b->ob_flags, nb),
-             p_fo = a.in(b->out_off, 8 * (o + 1));
-  const Part o_cnt = a.out(4 * o), o_ops = a.out(4 * o), o_sel = a.out(4 * o), o_res = a.out(o), o_cl = a.out(4 * cap),
-             o_op = a.out(cap), o_st = a.out(cap);
-  HIPCHK(c, hipEventRecord(stg.ev[0], c->stream));
-  if (int r = a.commit(c, stg.buf)) return r;
   DispatchDev d{};
   d.C = C;
   d.nw = route.words;
   d.O = O;
-  d.cluster_flags = a.ptr<const uint8_t>(stg.buf, p_cf);
-  d.obj_flags = a.ptr<const uint8_t>(stg.buf, p_of);
-  d.obj_ns = a.ptr<const int32_t>(stg.buf, p_ns);
-  d.obj_pl_off = a.ptr<const int32_t>(stg.buf, p_po);
-  d.pl_cluster = a.ptr<const int32_t>(stg.buf, p_pc);
-  d.ns_pl_off = a.ptr<const int32_t>(stg.buf, p_no);
-  d.ns_cluster = a.ptr<const int32_t>(stg.buf, p_nc);
-  d.obj_ob_off = a.ptr<const int32_t>(stg.buf, p_oo);
-  d.ob_cluster = a.ptr<const int32_t>(stg.buf, p_oc);
-  d.ob_flags = a.ptr<const uint8_t>(stg.buf, p_ob);
-  d.out_off = a.ptr<const int64_t>(stg.buf, p_fo);
-  d.count = a.ptr<int32_t>(stg.buf, o_cnt);
-  d.n_ops = a.ptr<int32_t>(stg.buf, o_ops);
-  d.n_selected = a.ptr<int32_t>(stg.buf, o_sel);
-  d.obj_result = a.ptr<uint8_t>(stg.buf, o_res);
-  d.out_cluster = a.ptr<int32_t>(stg.buf, o_cl);
-  d.out_op = a.ptr<uint8_t>(stg.buf, o_op);
-  d.out_status = a.ptr<uint8_t>(stg.buf, o_st);
+  Arena a;
+  a.in(d.cluster_flags, b->cluster_flags, (size_t)C);
+  a.in(d.obj_flags, b->obj_flags, o);
+  a.in(d.obj_ns, b->obj_ns, o);
+  a.in(d.obj_pl_off, b->obj_pl_off, o + 1);
+  a.in(d.pl_cluster, b->pl_cluster, np);
+  a.in(d.ns_pl_off, b->ns_pl_off, n + 1);
+  a.in(d.ns_cluster, b->ns_cluster, nn);
+  a.in(d.obj_ob_off, b->obj_ob_off, o + 1);
+  a.in(d.ob_cluster, b->ob_cluster, nb);
+  a.in(d.ob_flags, b->ob_flags, nb);
+  a.in(d.out_off, b->out_off, o + 1);
+  a.out(d.count, out->count, o);
+  a.out(d.n_ops, out->n_ops, o);
+  a.out(d.n_selected, out->n_selected, o);
+  a.out(d.obj_result, out->obj_result, o);
+  // the entries come back into a host staging area (below), not into the caller's arrays
+  a.out(d.out_cluster, cap);
+  a.out(d.out_op, cap);
+  a.out(d.out_status, cap);
+  HIPCHK(c, hipEventRecord(stg.ev[0], c->stream));
+  if (int r = a.commit(c, stg.buf)) return r;
   HIPCHK(c, hipEventRecord(stg.ev[1], c->stream));
   HIPCHK(c, launch_dispatch(d, route, c->stream));
   HIPCHK(c, hipEventRecord(stg.ev[2], c->stream));
   // the entries come back into a host staging area: only an object's first count[o] slots reach the caller's
   // arrays, the slack behind them stays as the caller left it
   std::vector<uint8_t>& hs = c->di_host;
-  if (hs.size() < 6 * cap) hs.resize(6 * cap);
+  const size_t cl_bytes = sizeof *d.out_cluster * cap;
+  if (hs.size() < cl_bytes + 2 * cap) hs.resize(cl_bytes + 2 * cap);
   int32_t* h_cl = reinterpret_cast<int32_t*>(hs.data());
-  uint8_t *h_op = hs.data() + 4 * cap, *h_st = h_op + cap;
-  HIPCHK(c, hipMemcpyAsync(out->count, d.count, 4 * o, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(out->n_ops, d.n_ops, 4 * o, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(out->n_selected, d.n_selected, 4 * o, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(out->obj_result, d.obj_result, o, hipMemcpyDeviceToHost, c->stream));
+  uint8_t *h_op = hs.data() + cl_bytes, *h_st = h_op + cap;
+  if (int r = a.fetch(c)) return r;
   if (cap) {
-    HIPCHK(c, hipMemcpyAsync(h_cl, d.out_cluster, 4 * cap, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(h_cl, d.out_cluster, cl_bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(h_op, d.out_op, cap, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(h_st, d.out_status, cap, hipMemcpyDeviceToHost, c->stream));
   }
   HIPCHK(c, hipEventRecord(stg.ev[3], c->stream));
-  stg.ran = true;
-  c->di_route = route;
+  stage_ran(stg, route);
   HIPCHK(c, hipStreamSynchronize(c->stream));
   const int64_t* fo = b->out_off;
   const int32_t* cnt = out->count;
@@ -281,7 +272,7 @@ static int dispatch_plan_locked(kad_ctx* c, const kad_dispatch_batch* b, const k
     for (int i = lo; i < hi; ++i) {
       const size_t at = (size_t)fo[i], k = (size_t)cnt[i];
       if (!k) continue;
-      memcpy(out->out_cluster + at, h_cl + at, 4 * k);
+      memcpy(out->out_cluster + at, h_cl + at, sizeof *h_cl * k);
       memcpy(out->out_op + at, h_op + at, k);
       memcpy(out->out_status + at, h_st + at, k);
     }
@@ -290,13 +281,11 @@ static int dispatch_plan_locked(kad_ctx* c, const kad_dispatch_batch* b, const k
 }
 
 int kad_dispatch_check(const kad_dispatch_batch* b, const kad_dispatch_view* out) {
-  try {
+  return check_guarded([&]() -> int {
     if (!b) return KAD_EINVAL;
     std::string err;
     return validate_dispatch(b, out, &err);
-  } catch (...) {
-    return KAD_EHOST;
-  }
+  });
 }
 
 int kad_dispatch_plan(kad_ctx* c, const kad_dispatch_batch* b, const kad_dispatch_view* out) {
@@ -314,25 +303,14 @@ int kad_dispatch_decide(uint32_t cluster_flags, int32_t selected, uint32_t ob_fl
   return KAD_OK;
 }
 
-int kad_dispatch_timing(kad_ctx* c, float ms[3]) {
-  return entry(c, ms != nullptr, [&] { return stage_timing(c, c->stage[STG_DISPATCH], 3, ms, "no kad_dispatch_plan ran"); });
-}
+int kad_dispatch_timing(kad_ctx* c, float ms[3]) { return stage_timing(c, STG_DISPATCH, 3, ms, "no kad_dispatch_plan ran"); }
 
 int kad_dispatch_route_eval(int32_t n_clusters, int32_t n_objects, int32_t n_cu, int32_t* out) {
   if (!out || n_clusters < 0 || n_objects < 0 || n_cu < 1) return KAD_EINVAL;
   if (n_clusters > DI_MAX_CLUSTERS) return KAD_EUNSUPPORTED;
-  const DispatchRoute r = route_dispatch(n_clusters, n_objects, n_cu);
-  static_assert(sizeof r == 4 * KAD_DISPATCH_ROUTE_FIELDS, "kad_dispatch_route_eval's record");
-  memcpy(out, &r, sizeof r);
-  return KAD_OK;
+  return route_record<KAD_DISPATCH_ROUTE_FIELDS>(out, route_dispatch(n_clusters, n_objects, n_cu));
 }
 
-int kad_dispatch_last_route(kad_ctx* c, int32_t* out) {
-  return entry(c, out != nullptr, [&]() -> int {
-    if (!c->stage[STG_DISPATCH].ran) return fail(c, KAD_ESTATE, "no kad_dispatch_plan ran");
-    memcpy(out, &c->di_route, sizeof c->di_route);
-    return KAD_OK;
-  });
-}
+int kad_dispatch_last_route(kad_ctx* c, int32_t* out) { return stage_last_route(c, STG_DISPATCH, out, "no kad_dispatch_plan ran"); }
 
 }  // extern "C"

@@ -219,24 +219,27 @@ int kad_explain(kad_ctx* c, const kad_profile* p, const int32_t* order, int n_or
     if (n_units == 0) return KAD_OK;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t n = (size_t)n_units, C = (size_t)c->sd.C;
-    Arena ar;
-    const Part p_units = ar.in(unit_idx, 4 * n), o_rej = ar.out(20 * n), o_feas = ar.out(4 * n),
-               o_fit = out->fit_detail ? ar.out(12 * n) : Arena::absent(),
-               o_ff = out->first_fail ? ar.out(n * C) : Arena::absent();
-    Stage& stg = c->stage[STG_EXPLAIN];
-    if (int r = ar.commit(c, stg.buf)) return r;
     ExplainArgs a{};
     a.s = c->sd;
     a.b = c->bd;
     a.filter_mask = p->filter_mask;
     a.order = packed;
     a.n_order = n_order;
-    a.units = ar.ptr<const int32_t>(stg.buf, p_units);
     a.n_units = n_units;
-    a.rejected = ar.ptr<int32_t>(stg.buf, o_rej);
-    a.feasible = ar.ptr<int32_t>(stg.buf, o_feas);
-    a.fit_detail = ar.ptr<int32_t>(stg.buf, o_fit);
-    a.first_fail = ar.ptr<uint8_t>(stg.buf, o_ff);
+    Arena ar;
+    ar.in(a.units, unit_idx, n);
+    ar.out(a.rejected, out->rejected, 5 * n);
+    ar.out(a.feasible, out->feasible, n);
+    if (out->fit_detail)
+      ar.out(a.fit_detail, out->fit_detail, 3 * n);
+    else
+      ar.absent(a.fit_detail);
+    if (out->first_fail)
+      ar.out(a.first_fail, out->first_fail, n * C);
+    else
+      ar.absent(a.first_fail);
+    Stage& stg = c->stage[STG_EXPLAIN];
+    if (int r = ar.commit(c, stg.buf)) return r;
     HIPCHK(c, hipEventRecord(stg.ev[0], c->stream));
     bool zeroed = false;
     HIPCHK(c, launch_req_masks(c->sd, c->bd, c->stream, false, &zeroed));
@@ -244,17 +247,12 @@ int kad_explain(kad_ctx* c, const kad_profile* p, const int32_t* order, int n_or
     HIPCHK(c, launch_explain(a, c->stream));
     HIPCHK(c, hipEventRecord(stg.ev[2], c->stream));
     stg.ran = true;
-    HIPCHK(c, hipMemcpyAsync(out->rejected, a.rejected, 20 * n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(out->feasible, a.feasible, 4 * n, hipMemcpyDeviceToHost, c->stream));
-    if (a.fit_detail) HIPCHK(c, hipMemcpyAsync(out->fit_detail, a.fit_detail, 12 * n, hipMemcpyDeviceToHost, c->stream));
-    if (a.first_fail && C) HIPCHK(c, hipMemcpyAsync(out->first_fail, a.first_fail, n * C, hipMemcpyDeviceToHost, c->stream));
+    if (int r = ar.fetch(c)) return r;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return KAD_OK;
   });
 }
 
-int kad_explain_timing(kad_ctx* c, float ms[2]) {
-  return entry(c, ms != nullptr, [&] { return stage_timing(c, c->stage[STG_EXPLAIN], 2, ms, "no kad_explain ran"); });
-}
+int kad_explain_timing(kad_ctx* c, float ms[2]) { return stage_timing(c, STG_EXPLAIN, 2, ms, "no kad_explain ran"); }
 
 }  // extern "C"

@@ -390,26 +390,11 @@ static int follower_union_locked(kad_ctx* c, const kad_follower_batch* b, const 
   // one buffer: the inputs, then changed / count / out_off / the scan's block sums / out_cluster
   const size_t f = (size_t)F, l = (size_t)L, n_lead = resident ? 0 : (size_t)b->lead_off[L],
                n_sched = resident && b->sched_off ? (size_t)b->sched_off[W] : 0, n_keep = b->keep_off ? (size_t)b->keep_off[L] : 0;
-  Arena a;
-  const Part p_lo = resident ? Arena::absent() : a.in(b->lead_off, 4 * (l + 1)), p_lc = a.in(b->lead_cluster, 4 * n_lead),
-             p_so = resident && b->sched_off ? a.in(b->sched_off, 4 * ((size_t)W + 1)) : Arena::absent(),
-             p_sc = a.in(b->sched_cluster, 4 * n_sched),
-             p_ko = b->keep_off ? a.in(b->keep_off, 4 * (l + 1)) : Arena::absent(), p_kc = a.in(b->keep_cluster, 4 * n_keep),
-             p_fo = a.in(b->fol_off, 4 * (f + 1)), p_fl = a.in(b->fol_leader, 4 * (size_t)b->fol_off[F]),
-             p_co = a.in(b->cur_off, 4 * (f + 1)), p_cc = a.in(b->cur_cluster, 4 * (size_t)b->cur_off[F]),
-             p_ch = a.in(b->cur_has, f);
-  const size_t scan_blocks = (f + 256 * FOL_SCAN_ITEMS - 1) / (256 * FOL_SCAN_ITEMS);
-  const Part o_changed = a.out(f), o_count = a.out(4 * f), o_off = a.out(8 * (f + 1)), o_sums = a.out(8 * scan_blocks),
-             o_cluster = a.out(4 * (size_t)b->out_capacity);
-  Stage& stg = c->stage[STG_FOLLOWER];
-  if (int r = a.commit(c, stg.buf)) return r;
   FollowerDev fd{};
   fd.n_ids = b->n_ids;
   fd.nw = route.words;
   fd.F = F;
   fd.n_leaders = L;
-  fd.lead_off = a.ptr<const int32_t>(stg.buf, p_lo);
-  fd.lead_cluster = a.ptr<const int32_t>(stg.buf, p_lc);
   fd.resident = resident ? 1 : 0;
   fd.W = (int)W;
   if (resident) {
@@ -421,54 +406,64 @@ static int follower_union_locked(kad_ctx* c, const kad_follower_batch* b, const 
     fd.res_cluster = c->d_cluster;
     fd.slot_lo = c->slot_lo;
   }
-  fd.sched_off = a.ptr<const int32_t>(stg.buf, p_so);
-  fd.sched_cluster = a.ptr<const int32_t>(stg.buf, p_sc);
-  fd.keep_off = a.ptr<const int32_t>(stg.buf, p_ko);
-  fd.keep_cluster = a.ptr<const int32_t>(stg.buf, p_kc);
-  fd.fol_off = a.ptr<const int32_t>(stg.buf, p_fo);
-  fd.fol_leader = a.ptr<const int32_t>(stg.buf, p_fl);
-  fd.fcur_off = a.ptr<const int32_t>(stg.buf, p_co);
-  fd.fcur_cluster = a.ptr<const int32_t>(stg.buf, p_cc);
-  fd.fcur_has = a.ptr<const uint8_t>(stg.buf, p_ch);
   fd.emit_all = (b->flags & KAD_FOL_EMIT_ALL) ? 1 : 0;
   fd.capacity = b->out_capacity;
-  fd.changed = a.ptr<uint8_t>(stg.buf, o_changed);
-  fd.count = a.ptr<int32_t>(stg.buf, o_count);
-  fd.fout_off = a.ptr<int64_t>(stg.buf, o_off);
-  fd.scan_sums = a.ptr<int64_t>(stg.buf, o_sums);
-  fd.out_cluster = a.ptr<int32_t>(stg.buf, o_cluster);
+  // an offset array the caller left out is absent; its id list keeps an (empty) slot
+  Arena a;
+  if (resident)
+    a.absent(fd.lead_off);
+  else
+    a.in(fd.lead_off, b->lead_off, l + 1);
+  a.in(fd.lead_cluster, b->lead_cluster, n_lead);
+  if (resident && b->sched_off)
+    a.in(fd.sched_off, b->sched_off, (size_t)W + 1);
+  else
+    a.absent(fd.sched_off);
+  a.in(fd.sched_cluster, b->sched_cluster, n_sched);
+  if (b->keep_off)
+    a.in(fd.keep_off, b->keep_off, l + 1);
+  else
+    a.absent(fd.keep_off);
+  a.in(fd.keep_cluster, b->keep_cluster, n_keep);
+  a.in(fd.fol_off, b->fol_off, f + 1);
+  a.in(fd.fol_leader, b->fol_leader, (size_t)b->fol_off[F]);
+  a.in(fd.fcur_off, b->cur_off, f + 1);
+  a.in(fd.fcur_cluster, b->cur_cluster, (size_t)b->cur_off[F]);
+  a.in(fd.fcur_has, b->cur_has, f);
+  a.out(fd.changed, out->changed, f);
+  a.out(fd.count, out->count, f);
+  a.out(fd.fout_off, out->out_off, f + 1);
+  a.out(fd.scan_sums, (f + 256 * FOL_SCAN_ITEMS - 1) / (256 * FOL_SCAN_ITEMS));  // the scan's block sums
+  a.out(fd.out_cluster, (size_t)b->out_capacity);  // copied below, once out_off[F] is known
+  Stage& stg = c->stage[STG_FOLLOWER];
+  if (int r = a.commit(c, stg.buf)) return r;
   HIPCHK(c, hipEventRecord(stg.ev[0], c->stream));
   HIPCHK(c, launch_follower_union(fd, route, c->stream));
   HIPCHK(c, hipEventRecord(stg.ev[1], c->stream));
   HIPCHK(c, launch_follower_scan(fd, c->stream));
   HIPCHK(c, launch_follower_emit(fd, route, c->stream));
   HIPCHK(c, hipEventRecord(stg.ev[2], c->stream));
-  stg.ran = true;
-  c->fol_route = route;
-  HIPCHK(c, hipMemcpyAsync(out->changed, fd.changed, f, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(out->count, fd.count, 4 * f, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(out->out_off, fd.fout_off, 8 * (f + 1), hipMemcpyDeviceToHost, c->stream));
+  stage_ran(stg, route);
+  if (int r = a.fetch(c)) return r;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   const int64_t n_out = out->out_off[F];
   if (n_out > b->out_capacity)
     return fail(c, KAD_ENOSPC, "out_capacity " + std::to_string(b->out_capacity) + " < " + std::to_string(n_out) +
                                    " emitted ids: retry with out_off[n_followers] slots");
   if (n_out) {
-    HIPCHK(c, hipMemcpyAsync(out->out_cluster, fd.out_cluster, 4 * (size_t)n_out, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out->out_cluster, fd.out_cluster, sizeof *fd.out_cluster * (size_t)n_out, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
   return KAD_OK;
 }
 
 int kad_follower_check(const kad_follower_batch* b, const kad_follower_view* out, int32_t n_clusters, int32_t n_units) {
-  try {
+  return check_guarded([&]() -> int {
     if (!b || n_clusters < 0) return KAD_EINVAL;
     if (!b->lead_off && n_units < 0) return KAD_ESTATE;
     std::string err;
     return validate_follower(b, out, n_clusters, b->lead_off ? 0 : n_units, &err);
-  } catch (...) {
-    return KAD_EHOST;
-  }
+  });
 }
 
 int kad_follower_union(kad_ctx* c, const kad_follower_batch* b, const kad_follower_view* out) {
@@ -477,24 +472,13 @@ int kad_follower_union(kad_ctx* c, const kad_follower_batch* b, const kad_follow
   });
 }
 
-int kad_follower_timing(kad_ctx* c, float ms[2]) {
-  return entry(c, ms != nullptr, [&] { return stage_timing(c, c->stage[STG_FOLLOWER], 2, ms, "no kad_follower_union ran"); });
-}
+int kad_follower_timing(kad_ctx* c, float ms[2]) { return stage_timing(c, STG_FOLLOWER, 2, ms, "no kad_follower_union ran"); }
 
 int kad_follower_route_eval(int32_t n_ids, int32_t n_followers, int32_t n_cu, int32_t* out) {
   if (!out || n_ids < 0 || n_ids > FOL_MAX_IDS || n_followers < 0 || n_cu < 1) return KAD_EINVAL;
-  const FollowerRoute r = route_follower(n_ids, n_followers, n_cu);
-  static_assert(sizeof r == 4 * KAD_FOL_ROUTE_FIELDS, "kad_follower_route_eval's record");
-  memcpy(out, &r, sizeof r);
-  return KAD_OK;
+  return route_record<KAD_FOL_ROUTE_FIELDS>(out, route_follower(n_ids, n_followers, n_cu));
 }
 
-int kad_follower_last_route(kad_ctx* c, int32_t* out) {
-  return entry(c, out != nullptr, [&]() -> int {
-    if (!c->stage[STG_FOLLOWER].ran) return fail(c, KAD_ESTATE, "no kad_follower_union ran");
-    memcpy(out, &c->fol_route, sizeof c->fol_route);
-    return KAD_OK;
-  });
-}
+int kad_follower_last_route(kad_ctx* c, int32_t* out) { return stage_last_route(c, STG_FOLLOWER, out, "no kad_follower_union ran"); }
 
 }  // extern "C"

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "kad_groups.h"
+
 namespace kad {
 
 constexpr int MIG_MAX_IDS = 131072;    // the id space of kad_follower_union
@@ -58,26 +60,17 @@ struct MigrateRoute {
   int32_t obj_grid;    // blocks of the object kernel
 };
 
-inline int mig_width(int64_t items, int64_t rows) {
-  const int64_t mean = rows > 0 ? (items + rows - 1) / rows : 0;
-  int w = MIG_MIN_WIDTH;
-  while (w < 64 && w < mean) w <<= 1;
-  return w;
-}
-
 inline MigrateRoute route_migrate(int S, int64_t P, int n_long, int O, int n_cu) {
   MigrateRoute r{};
-  r.width = mig_width(P, S);
+  r.width = group_width(P, S, MIG_MIN_WIDTH, 1);
   r.long_min = MIG_LONG_MIN;
   r.threads = 256;
-  // no LDS on the group path: 8 blocks (32 waves) a CU, each lane group striding
-  const int64_t per_block = 256 / r.width, want = ((int64_t)S + per_block - 1) / per_block, cap = (int64_t)n_cu * 8;
-  r.grid = (int32_t)(want < cap ? want : cap);
+  // no LDS on the group path
+  r.grid = group_grid(S, r.width, n_cu);
   r.long_grid = n_long;
-  r.stride = (int32_t)(r.grid * per_block);
-  r.obj_width = mig_width(S, O);
-  const int64_t oper = 256 / r.obj_width, owant = ((int64_t)O + oper - 1) / oper;
-  r.obj_grid = (int32_t)(owant < cap ? owant : cap);
+  r.stride = group_stride(r.grid, r.width);
+  r.obj_width = group_width(S, O, MIG_MIN_WIDTH, 1);
+  r.obj_grid = group_grid(O, r.obj_width, n_cu);
   return r;
 }
 

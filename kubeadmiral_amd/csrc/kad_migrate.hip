@@ -208,28 +208,20 @@ __global__ __launch_bounds__(256) void migrate_object_kernel(MigrateDev d) {
 hipError_t launch_migrate_segments(const MigrateDev& d, const MigrateRoute& r, hipStream_t st) {
   (void)hipGetLastError();
   const unsigned grid = (unsigned)(r.grid + r.long_grid);
-  if (grid > 0) {
-    switch (r.width) {
-      case 8: hipLaunchKernelGGL(migrate_segment_kernel<8>, dim3(grid), dim3(256), 0, st, d); break;
-      case 16: hipLaunchKernelGGL(migrate_segment_kernel<16>, dim3(grid), dim3(256), 0, st, d); break;
-      case 32: hipLaunchKernelGGL(migrate_segment_kernel<32>, dim3(grid), dim3(256), 0, st, d); break;
-      default: hipLaunchKernelGGL(migrate_segment_kernel<64>, dim3(grid), dim3(256), 0, st, d); break;
-    }
-  }
+  if (grid > 0)
+    with_width<MIG_MIN_WIDTH>(r.width, [&](auto W) {
+      hipLaunchKernelGGL(migrate_segment_kernel<decltype(W)::value>, dim3(grid), dim3(256), 0, st, d);
+    });
   return hipGetLastError();
 }
 
 hipError_t launch_migrate_objects(const MigrateDev& d, const MigrateRoute& r, hipStream_t st) {
   (void)hipGetLastError();
   const unsigned grid = (unsigned)r.obj_grid;
-  if (grid > 0) {
-    switch (r.obj_width) {
-      case 8: hipLaunchKernelGGL(migrate_object_kernel<8>, dim3(grid), dim3(256), 0, st, d); break;
-      case 16: hipLaunchKernelGGL(migrate_object_kernel<16>, dim3(grid), dim3(256), 0, st, d); break;
-      case 32: hipLaunchKernelGGL(migrate_object_kernel<32>, dim3(grid), dim3(256), 0, st, d); break;
-      default: hipLaunchKernelGGL(migrate_object_kernel<64>, dim3(grid), dim3(256), 0, st, d); break;
-    }
-  }
+  if (grid > 0)
+    with_width<MIG_MIN_WIDTH>(r.obj_width, [&](auto W) {
+      hipLaunchKernelGGL(migrate_object_kernel<decltype(W)::value>, dim3(grid), dim3(256), 0, st, d);
+    });
   return hipGetLastError();
 }
 
@@ -323,7 +315,8 @@ static int validate_migrate(const kad_migrate_batch* b, const kad_migrate_view* 
 
 static int migrate_estimate_locked(kad_ctx* c, const kad_migrate_batch* b, const kad_migrate_view* out) {
   if (!c->have_snapshot) return fail(c, KAD_ESTATE, "a snapshot must be uploaded first");
-  const int long_min = c->mig_force_long_min > 0 ? c->mig_force_long_min : MIG_LONG_MIN;
+  Stage& stg = c->stage[STG_MIGRATE];
+  const int long_min = stg.force.long_min_or(MIG_LONG_MIN);
   std::string err;
   std::vector<int32_t> seg_obj, long_list;
   if (int r = validate_migrate(b, out, c->sd.C, long_min, &seg_obj, &long_list, &err)) return fail(c, r, err);
@@ -332,25 +325,10 @@ static int migrate_estimate_locked(kad_ctx* c, const kad_migrate_batch* b, const
   if (O == 0) return KAD_OK;
   HIPCHK(c, hipSetDevice(c->device));
   MigrateRoute route = route_migrate(S, P, (int)long_list.size(), O, n_cus());
-  if (c->mig_force_width > 0) {
-    route.width = c->mig_force_width;
-    const int64_t per = 256 / route.width, want = ((int64_t)S + per - 1) / per, cap = (int64_t)n_cus() * 8;
-    route.grid = (int32_t)(want < cap ? want : cap);
-    route.stride = (int32_t)(route.grid * per);
-  }
+  group_force_apply(stg.force, true, S, n_cus(), route.width, route.grid, &route.stride);  // even when every segment is long
   route.long_min = long_min;
   // one buffer: the inputs, then the outputs
   const size_t o = (size_t)O, sg = (size_t)S, pd = (size_t)P, n = (size_t)N, nl = long_list.size();
-  Arena a;
-  const Part p_so = a.in(b->obj_seg_off, 4 * (o + 1)), p_th = a.in(b->obj_threshold_ns, 8 * o),
-             p_sj = a.in(seg_obj.data(), 4 * sg), p_sc = a.in(b->seg_cluster, 4 * sg), p_sd = a.in(b->seg_desired, 8 * sg),
-             p_sf = a.in(b->seg_flags, sg), p_po = a.in(b->seg_pod_off, 8 * (sg + 1)), p_pt = a.in(b->pod_t_ns, 8 * pd),
-             p_pf = a.in(b->pod_flags, pd), p_ll = a.in(long_list.data(), 4 * nl), p_oo = a.in(b->old_off, 4 * (o + 1)),
-             p_oc = a.in(b->old_cluster, 4 * n), p_ov = a.in(b->old_cap, 8 * n);
-  const Part o_uns = a.out(4 * sg), o_next = a.out(8 * sg), o_cap = a.out(8 * sg), o_changed = a.out(o),
-             o_written = a.out(4 * o), o_retry = a.out(8 * o), o_backoff = a.out(o);
-  Stage& stg = c->stage[STG_MIGRATE];
-  if (int r = a.commit(c, stg.buf)) return r;
   MigrateDev md{};
   md.O = O;
   md.S = S;
@@ -359,54 +337,45 @@ static int migrate_estimate_locked(kad_ctx* c, const kad_migrate_batch* b, const
   md.obj_width = route.obj_width;
   md.long_min = route.long_min;
   md.n_long = (int)nl;
-  md.obj_seg_off = a.ptr<const int32_t>(stg.buf, p_so);
-  md.obj_thr = a.ptr<const int64_t>(stg.buf, p_th);
-  md.seg_obj = a.ptr<const int32_t>(stg.buf, p_sj);
-  md.seg_cluster = a.ptr<const int32_t>(stg.buf, p_sc);
-  md.seg_desired = a.ptr<const int64_t>(stg.buf, p_sd);
-  md.seg_flags = a.ptr<const uint8_t>(stg.buf, p_sf);
-  md.seg_pod_off = a.ptr<const int64_t>(stg.buf, p_po);
-  md.pod_t = a.ptr<const int64_t>(stg.buf, p_pt);
-  md.pod_flags = a.ptr<const uint8_t>(stg.buf, p_pf);
-  md.long_list = a.ptr<const int32_t>(stg.buf, p_ll);
-  md.old_off = a.ptr<const int32_t>(stg.buf, p_oo);
-  md.old_cluster = a.ptr<const int32_t>(stg.buf, p_oc);
-  md.old_cap = a.ptr<const int64_t>(stg.buf, p_ov);
-  md.uns = a.ptr<int32_t>(stg.buf, o_uns);
-  md.next_cross = a.ptr<int64_t>(stg.buf, o_next);
-  md.cap = a.ptr<int64_t>(stg.buf, o_cap);
-  md.changed = a.ptr<uint8_t>(stg.buf, o_changed);
-  md.n_written = a.ptr<int32_t>(stg.buf, o_written);
-  md.retry_after = a.ptr<int64_t>(stg.buf, o_retry);
-  md.backoff = a.ptr<uint8_t>(stg.buf, o_backoff);
+  Arena a;
+  a.in(md.obj_seg_off, b->obj_seg_off, o + 1);
+  a.in(md.obj_thr, b->obj_threshold_ns, o);
+  a.in(md.seg_obj, seg_obj.data(), sg);
+  a.in(md.seg_cluster, b->seg_cluster, sg);
+  a.in(md.seg_desired, b->seg_desired, sg);
+  a.in(md.seg_flags, b->seg_flags, sg);
+  a.in(md.seg_pod_off, b->seg_pod_off, sg + 1);
+  a.in(md.pod_t, b->pod_t_ns, pd);
+  a.in(md.pod_flags, b->pod_flags, pd);
+  a.in(md.long_list, long_list.data(), nl);
+  a.in(md.old_off, b->old_off, o + 1);
+  a.in(md.old_cluster, b->old_cluster, n);
+  a.in(md.old_cap, b->old_cap, n);
+  a.out(md.uns, out->uns, sg);
+  a.out(md.next_cross, out->next_cross, sg);
+  a.out(md.cap, out->cap, sg);
+  a.out(md.changed, out->changed, o);
+  a.out(md.n_written, out->n_written, o);
+  a.out(md.retry_after, out->retry_after, o);
+  a.out(md.backoff, out->backoff, o);
+  if (int r = a.commit(c, stg.buf)) return r;
   HIPCHK(c, hipEventRecord(stg.ev[0], c->stream));
   HIPCHK(c, launch_migrate_segments(md, route, c->stream));
   HIPCHK(c, hipEventRecord(stg.ev[1], c->stream));
   HIPCHK(c, launch_migrate_objects(md, route, c->stream));
   HIPCHK(c, hipEventRecord(stg.ev[2], c->stream));
-  stg.ran = true;
-  c->mig_route = route;
-  if (S) {
-    HIPCHK(c, hipMemcpyAsync(out->uns, md.uns, 4 * sg, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(out->next_cross, md.next_cross, 8 * sg, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(out->cap, md.cap, 8 * sg, hipMemcpyDeviceToHost, c->stream));
-  }
-  HIPCHK(c, hipMemcpyAsync(out->changed, md.changed, o, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(out->n_written, md.n_written, 4 * o, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(out->retry_after, md.retry_after, 8 * o, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(out->backoff, md.backoff, o, hipMemcpyDeviceToHost, c->stream));
+  stage_ran(stg, route);
+  if (int r = a.fetch(c)) return r;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return KAD_OK;
 }
 
 int kad_migrate_check(const kad_migrate_batch* b, const kad_migrate_view* out, int32_t n_clusters) {
-  try {
+  return check_guarded([&]() -> int {
     if (!b || n_clusters < 0) return KAD_EINVAL;
     std::string err;
     return validate_migrate(b, out, n_clusters, MIG_LONG_MIN, nullptr, nullptr, &err);
-  } catch (...) {
-    return KAD_EHOST;
-  }
+  });
 }
 
 int kad_migrate_estimate(kad_ctx* c, const kad_migrate_batch* b, const kad_migrate_view* out) {
@@ -415,35 +384,19 @@ int kad_migrate_estimate(kad_ctx* c, const kad_migrate_batch* b, const kad_migra
   });
 }
 
-int kad_migrate_timing(kad_ctx* c, float ms[2]) {
-  return entry(c, ms != nullptr, [&] { return stage_timing(c, c->stage[STG_MIGRATE], 2, ms, "no kad_migrate_estimate ran"); });
-}
+int kad_migrate_timing(kad_ctx* c, float ms[2]) { return stage_timing(c, STG_MIGRATE, 2, ms, "no kad_migrate_estimate ran"); }
 
 int kad_migrate_route_eval(int32_t n_segments, int64_t n_pods, int32_t n_long, int32_t n_objects, int32_t n_cu,
                            int32_t* out) {
   if (!out || n_segments < 0 || n_pods < 0 || n_long < 0 || n_long > n_segments || n_objects < 0 || n_cu < 1)
     return KAD_EINVAL;
-  const MigrateRoute r = route_migrate(n_segments, n_pods, n_long, n_objects, n_cu);
-  static_assert(sizeof r == 4 * KAD_MIG_ROUTE_FIELDS, "kad_migrate_route_eval's record");
-  memcpy(out, &r, sizeof r);
-  return KAD_OK;
+  return route_record<KAD_MIG_ROUTE_FIELDS>(out, route_migrate(n_segments, n_pods, n_long, n_objects, n_cu));
 }
 
-int kad_migrate_last_route(kad_ctx* c, int32_t* out) {
-  return entry(c, out != nullptr, [&]() -> int {
-    if (!c->stage[STG_MIGRATE].ran) return fail(c, KAD_ESTATE, "no kad_migrate_estimate ran");
-    memcpy(out, &c->mig_route, sizeof c->mig_route);
-    return KAD_OK;
-  });
-}
+int kad_migrate_last_route(kad_ctx* c, int32_t* out) { return stage_last_route(c, STG_MIGRATE, out, "no kad_migrate_estimate ran"); }
 
 int kad_migrate_debug_route(kad_ctx* c, int32_t force_width, int32_t force_long_min) {
-  const bool width_ok = force_width == 0 || force_width == 8 || force_width == 16 || force_width == 32 || force_width == 64;
-  return entry(c, force_long_min >= 0 && width_ok, [&]() -> int {
-    c->mig_force_width = force_width;
-    c->mig_force_long_min = force_long_min;
-    return KAD_OK;
-  });
+  return stage_debug_route(c, STG_MIGRATE, group_width_ok(force_width, MIG_MIN_WIDTH), GroupForce{force_width, force_long_min, 0});
 }
 
 }  // extern "C"

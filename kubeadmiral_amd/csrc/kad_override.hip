@@ -391,12 +391,18 @@ static int override_match_locked(kad_ctx* c, const kad_override_batch* b, const 
   if (n_slots && !out->matched) return fail(c, KAD_EINVAL, "output view missing");
   HIPCHK(c, hipSetDevice(c->device));
   // one buffer: obj_policy, place_off, place_cluster, then status and the matched rows
-  const size_t m_bytes = 4 * (size_t)n_slots * RW;
+  OverrideDev o{};
   Arena a;
-  const Part p_op = a.in(b->obj_policy, 8 * (size_t)n),
-             p_po = from_results ? Arena::absent() : a.in(b->place_off, 4 * ((size_t)n + 1)),
-             p_pc = from_results ? Arena::absent() : a.in(b->place_cluster, 4 * (size_t)n_slots),
-             o_st = a.out(4 * (size_t)n), o_m = a.out(m_bytes);
+  a.in(o.obj_policy, b->obj_policy, 2 * (size_t)n);
+  if (from_results) {
+    a.absent(o.place_off);
+    a.absent(o.place_cluster);
+  } else {
+    a.in(o.place_off, b->place_off, (size_t)n + 1);
+    a.in(o.place_cluster, b->place_cluster, (size_t)n_slots);
+  }
+  a.out(o.status, out->status, (size_t)n);
+  a.out(o.matched, out->matched, (size_t)n_slots * RW);
   Stage& stg = c->stage[STG_OVERRIDE];
   if (int r = a.commit(c, stg.buf)) return r;
   const size_t nch = (size_t)((C + 63) / 64);
@@ -413,7 +419,6 @@ static int override_match_locked(kad_ctx* c, const kad_override_batch* b, const 
   rb.req_seg = reinterpret_cast<const int4*>(rb.req_perm + (size_t)c->ovr_n_seg_reqs * 8);
   rb.n_rowreq = c->ovr_n_rowreq;
   rb.req_rows = reinterpret_cast<const int4*>(reinterpret_cast<const int32_t*>(rb.req_seg) + 4 * (size_t)c->ovr_n_seg);
-  OverrideDev o{};
   o.C = C;
   o.P = P;
   o.R = h.n_rules;
@@ -428,7 +433,6 @@ static int override_match_locked(kad_ctx* c, const kad_override_batch* b, const 
   o.E = o.M + (size_t)h.n_rules * nch;
   o.n_obj = n;
   o.RW = RW;
-  o.obj_policy = a.ptr<const int32_t>(stg.buf, p_op);
   o.from_results = from_results ? 1 : 0;
   if (from_results) {
     o.out_off = c->bd.out_off;
@@ -441,11 +445,7 @@ static int override_match_locked(kad_ctx* c, const kad_override_batch* b, const 
     o.n_out = c->slot_n;
     o.cur_lo = c->cur_lo;
   }
-  o.place_off = a.ptr<const int32_t>(stg.buf, p_po);
-  o.place_cluster = a.ptr<const int32_t>(stg.buf, p_pc);
   o.n_slots = n_slots;
-  o.status = a.ptr<int32_t>(stg.buf, o_st);
-  o.matched = a.ptr<uint32_t>(stg.buf, o_m);
   HIPCHK(c, hipEventRecord(stg.ev[0], c->stream));
   bool zeroed = false;
   HIPCHK(c, launch_req_masks(c->sd, rb, c->stream, false, &zeroed));
@@ -455,8 +455,7 @@ static int override_match_locked(kad_ctx* c, const kad_override_batch* b, const 
   HIPCHK(c, launch_override_match(o, c->stream));
   HIPCHK(c, hipEventRecord(stg.ev[3], c->stream));
   stg.ran = true;
-  HIPCHK(c, hipMemcpyAsync(out->status, o.status, 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-  if (m_bytes) HIPCHK(c, hipMemcpyAsync(out->matched, o.matched, m_bytes, hipMemcpyDeviceToHost, c->stream));
+  if (int r = a.fetch(c)) return r;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return KAD_OK;
 }
@@ -490,8 +489,6 @@ int kad_override_match(kad_ctx* c, const kad_override_batch* b, const kad_overri
   });
 }
 
-int kad_override_timing(kad_ctx* c, float ms[3]) {
-  return entry(c, ms != nullptr, [&] { return stage_timing(c, c->stage[STG_OVERRIDE], 3, ms, "no kad_override_match ran"); });
-}
+int kad_override_timing(kad_ctx* c, float ms[3]) { return stage_timing(c, STG_OVERRIDE, 3, ms, "no kad_override_match ran"); }
 
 }  // extern "C"

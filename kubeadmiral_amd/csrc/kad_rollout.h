@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "kad_groups.h"
+
 namespace kad {
 
 // rows of tgt_vals: TargetStatus (pkg/controllers/util/rolloutplan.go:166-177) without Updated, then DesiredReplicas
@@ -184,28 +186,15 @@ struct RolloutRoute {
   int32_t serial;     // objects on the serial walk
 };
 
-inline int rollout_width(int64_t targets, int64_t objects) {
-  const int64_t mean = objects > 0 ? (targets + objects - 1) / objects : 0;
-  int w = 1;
-  while (w < 64 && w < mean) w <<= 1;
-  return w;
-}
-
-inline int32_t rollout_grid(int64_t objects, int width, int n_cu) {
-  // no LDS: 8 blocks (32 waves) a CU, each lane group striding
-  const int64_t per_block = 256 / width, want = (objects + per_block - 1) / per_block, cap = (int64_t)n_cu * 8;
-  return (int32_t)(want < cap ? want : cap);
-}
-
 inline RolloutRoute route_rollout(int O, int n_long, int64_t short_targets, int n_serial, int n_cu) {
   RolloutRoute r{};
   const int n_short = O - n_long;
-  r.width = rollout_width(short_targets, n_short);
+  r.width = group_width(short_targets, n_short, 1, 1);
   r.long_min = RO_LONG_MIN;
   r.threads = 256;
-  r.grid = n_short > 0 ? rollout_grid(O, r.width, n_cu) : 0;
+  r.grid = n_short > 0 ? group_grid(O, r.width, n_cu) : 0;  // no LDS
   r.long_grid = (n_long + 3) / 4;
-  r.stride = r.grid * (256 / r.width);
+  r.stride = group_stride(r.grid, r.width);
   r.serial = n_serial;
   return r;
 }

@@ -337,17 +337,10 @@ __global__ __launch_bounds__(256) void rollout_kernel(RolloutDev d, int long_gri
 hipError_t launch_rollout(const RolloutDev& d, const RolloutRoute& r, hipStream_t st) {
   (void)hipGetLastError();
   const unsigned grid = (unsigned)(r.grid + r.long_grid);
-  if (grid > 0) {
-    switch (r.width) {
-      case 1: hipLaunchKernelGGL((rollout_kernel<1>), dim3(grid), dim3(256), 0, st, d, r.long_grid); break;
-      case 2: hipLaunchKernelGGL((rollout_kernel<2>), dim3(grid), dim3(256), 0, st, d, r.long_grid); break;
-      case 4: hipLaunchKernelGGL((rollout_kernel<4>), dim3(grid), dim3(256), 0, st, d, r.long_grid); break;
-      case 8: hipLaunchKernelGGL((rollout_kernel<8>), dim3(grid), dim3(256), 0, st, d, r.long_grid); break;
-      case 16: hipLaunchKernelGGL((rollout_kernel<16>), dim3(grid), dim3(256), 0, st, d, r.long_grid); break;
-      case 32: hipLaunchKernelGGL((rollout_kernel<32>), dim3(grid), dim3(256), 0, st, d, r.long_grid); break;
-      default: hipLaunchKernelGGL((rollout_kernel<64>), dim3(grid), dim3(256), 0, st, d, r.long_grid); break;
-    }
-  }
+  if (grid > 0)
+    with_width<1>(r.width, [&](auto W) {
+      hipLaunchKernelGGL((rollout_kernel<decltype(W)::value>), dim3(grid), dim3(256), 0, st, d, r.long_grid);
+    });
   return hipGetLastError();
 }
 
@@ -367,8 +360,6 @@ struct RolloutPlanHost {
   int64_t short_targets = 0;
   int n_serial = 0;
 };
-
-bool rollout_width_ok(int w) { return w == 0 || (w >= 1 && w <= 64 && (w & (w - 1)) == 0); }
 
 int64_t abs64(int32_t v) { return v < 0 ? -(int64_t)v : (int64_t)v; }
 
@@ -440,75 +431,56 @@ static int validate_rollout(const kad_rollout_batch* b, const kad_rollout_view* 
 }
 
 static int rollout_plan_locked(kad_ctx* c, const kad_rollout_batch* b, const kad_rollout_view* out) {
-  const int long_min = c->ro_force_long_min > 0 ? c->ro_force_long_min : RO_LONG_MIN;
+  Stage& stg = c->stage[STG_ROLLOUT];
+  const int long_min = stg.force.long_min_or(RO_LONG_MIN);
   std::string err;
   RolloutPlanHost plan;
-  if (int r = validate_rollout(b, out, long_min, c->ro_force_serial != 0, &plan, nullptr, &err)) return fail(c, r, err);
+  if (int r = validate_rollout(b, out, long_min, stg.force.serial != 0, &plan, nullptr, &err)) return fail(c, r, err);
   const int O = b->n_objects, T = b->n_targets;
   if (O == 0) return KAD_OK;
   HIPCHK(c, hipSetDevice(c->device));
   const int n_long = (int)plan.long_list.size();
   RolloutRoute route = route_rollout(O, n_long, plan.short_targets, plan.n_serial, n_cus());
-  if (c->ro_force_width > 0 && n_long < O) {
-    route.width = c->ro_force_width;
-    route.grid = rollout_grid(O, route.width, n_cus());
-    route.stride = route.grid * (256 / route.width);
-  }
+  group_force_apply(stg.force, n_long < O, O, n_cus(), route.width, route.grid, &route.stride);
   route.long_min = long_min;
   // one buffer: the inputs, then the outputs
   const size_t o = (size_t)O, t = (size_t)T, nl = (size_t)n_long;
-  Arena a;
-  const Part p_to = a.in(b->obj_tgt_off, 4 * (o + 1)), p_ms = a.in(b->obj_max_surge, 4 * o),
-             p_mu = a.in(b->obj_max_unavailable, 4 * o), p_rp = a.in(b->obj_replicas, 4 * o), p_of = a.in(b->obj_flags, o),
-             p_tv = a.in(b->tgt_vals, 4 * (size_t)RO_NV * t), p_tf = a.in(b->tgt_flags, t),
-             p_om = a.in(plan.obj_mode.data(), o), p_ll = a.in(plan.long_list.data(), 4 * nl);
-  const Part o_r = a.out(4 * t), o_s = a.out(4 * t), o_u = a.out(4 * t), o_f = a.out(t), o_a = a.out(t), o_st = a.out(o);
-  Stage& stg = c->stage[STG_ROLLOUT];
-  if (int r = a.commit(c, stg.buf)) return r;
   RolloutDev d{};
   d.O = O;
   d.T = T;
   d.n_long = n_long;
-  d.obj_tgt_off = a.ptr<const int32_t>(stg.buf, p_to);
-  d.obj_max_surge = a.ptr<const int32_t>(stg.buf, p_ms);
-  d.obj_max_unavailable = a.ptr<const int32_t>(stg.buf, p_mu);
-  d.obj_replicas = a.ptr<const int32_t>(stg.buf, p_rp);
-  d.obj_flags = a.ptr<const uint8_t>(stg.buf, p_of);
-  d.tgt_vals = a.ptr<const int32_t>(stg.buf, p_tv);
-  d.tgt_flags = a.ptr<const uint8_t>(stg.buf, p_tf);
-  d.obj_mode = a.ptr<const uint8_t>(stg.buf, p_om);
-  d.long_list = a.ptr<const int32_t>(stg.buf, p_ll);
-  d.replicas = a.ptr<int32_t>(stg.buf, o_r);
-  d.max_surge = a.ptr<int32_t>(stg.buf, o_s);
-  d.max_unavailable = a.ptr<int32_t>(stg.buf, o_u);
-  d.plan_flags = a.ptr<uint8_t>(stg.buf, o_f);
-  d.action = a.ptr<uint8_t>(stg.buf, o_a);
-  d.status = a.ptr<uint8_t>(stg.buf, o_st);
+  Arena a;
+  a.in(d.obj_tgt_off, b->obj_tgt_off, o + 1);
+  a.in(d.obj_max_surge, b->obj_max_surge, o);
+  a.in(d.obj_max_unavailable, b->obj_max_unavailable, o);
+  a.in(d.obj_replicas, b->obj_replicas, o);
+  a.in(d.obj_flags, b->obj_flags, o);
+  a.in(d.tgt_vals, b->tgt_vals, (size_t)RO_NV * t);
+  a.in(d.tgt_flags, b->tgt_flags, t);
+  a.in(d.obj_mode, plan.obj_mode.data(), o);
+  a.in(d.long_list, plan.long_list.data(), nl);
+  a.out(d.replicas, out->replicas, t);
+  a.out(d.max_surge, out->max_surge, t);
+  a.out(d.max_unavailable, out->max_unavailable, t);
+  a.out(d.plan_flags, out->plan_flags, t);
+  a.out(d.action, out->action, t);
+  a.out(d.status, out->status, o);
+  if (int r = a.commit(c, stg.buf)) return r;
   HIPCHK(c, hipEventRecord(stg.ev[0], c->stream));
   HIPCHK(c, launch_rollout(d, route, c->stream));
   HIPCHK(c, hipEventRecord(stg.ev[1], c->stream));
-  stg.ran = true;
-  c->ro_route = route;
-  if (T) {
-    HIPCHK(c, hipMemcpyAsync(out->replicas, d.replicas, 4 * t, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(out->max_surge, d.max_surge, 4 * t, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(out->max_unavailable, d.max_unavailable, 4 * t, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(out->plan_flags, d.plan_flags, t, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(out->action, d.action, t, hipMemcpyDeviceToHost, c->stream));
-  }
-  HIPCHK(c, hipMemcpyAsync(out->status, d.status, o, hipMemcpyDeviceToHost, c->stream));
+  stage_ran(stg, route);
+  if (int r = a.fetch(c)) return r;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return KAD_OK;
 }
 
 int kad_rollout_check(const kad_rollout_batch* b, const kad_rollout_view* out, uint8_t* nowrap) {
-  try {
+  return check_guarded([&]() -> int {
     if (!b) return KAD_EINVAL;
     std::string err;
     return validate_rollout(b, out, RO_LONG_MIN, false, nullptr, nowrap, &err);
-  } catch (...) {
-    return KAD_EHOST;
-  }
+  });
 }
 
 int kad_rollout_plan(kad_ctx* c, const kad_rollout_batch* b, const kad_rollout_view* out) {
@@ -517,35 +489,20 @@ int kad_rollout_plan(kad_ctx* c, const kad_rollout_batch* b, const kad_rollout_v
   });
 }
 
-int kad_rollout_timing(kad_ctx* c, float ms[1]) {
-  return entry(c, ms != nullptr, [&] { return stage_timing(c, c->stage[STG_ROLLOUT], 1, ms, "no kad_rollout_plan ran"); });
-}
+int kad_rollout_timing(kad_ctx* c, float ms[1]) { return stage_timing(c, STG_ROLLOUT, 1, ms, "no kad_rollout_plan ran"); }
 
 int kad_rollout_route_eval(int32_t n_objects, int32_t n_long, int64_t short_targets, int32_t n_serial, int32_t n_cu, int32_t* out) {
   if (!out || n_objects < 0 || n_long < 0 || n_long > n_objects || short_targets < 0 || n_serial < 0 || n_serial > n_objects ||
       n_cu < 1)
     return KAD_EINVAL;
-  const RolloutRoute r = route_rollout(n_objects, n_long, short_targets, n_serial, n_cu);
-  static_assert(sizeof r == 4 * KAD_ROLLOUT_ROUTE_FIELDS, "kad_rollout_route_eval's record");
-  memcpy(out, &r, sizeof r);
-  return KAD_OK;
+  return route_record<KAD_ROLLOUT_ROUTE_FIELDS>(out, route_rollout(n_objects, n_long, short_targets, n_serial, n_cu));
 }
 
-int kad_rollout_last_route(kad_ctx* c, int32_t* out) {
-  return entry(c, out != nullptr, [&]() -> int {
-    if (!c->stage[STG_ROLLOUT].ran) return fail(c, KAD_ESTATE, "no kad_rollout_plan ran");
-    memcpy(out, &c->ro_route, sizeof c->ro_route);
-    return KAD_OK;
-  });
-}
+int kad_rollout_last_route(kad_ctx* c, int32_t* out) { return stage_last_route(c, STG_ROLLOUT, out, "no kad_rollout_plan ran"); }
 
 int kad_rollout_debug_route(kad_ctx* c, int32_t force_width, int32_t force_long_min, int32_t force_serial) {
-  return entry(c, force_long_min >= 0 && rollout_width_ok(force_width) && (force_serial == 0 || force_serial == 1), [&]() -> int {
-    c->ro_force_width = force_width;
-    c->ro_force_long_min = force_long_min;
-    c->ro_force_serial = force_serial;
-    return KAD_OK;
-  });
+  return stage_debug_route(c, STG_ROLLOUT, group_width_ok(force_width, 1) && (force_serial == 0 || force_serial == 1),
+                           GroupForce{force_width, force_long_min, force_serial});
 }
 
 }  // extern "C"

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "kad_groups.h"
+
 namespace kad {
 
 constexpr int SAGG_DEPLOYMENT = 0, SAGG_JOB = 1;  // KAD_SAGG_DEPLOYMENT / KAD_SAGG_JOB
@@ -55,30 +57,16 @@ struct SaggRoute {
   int32_t stride;     // objects between two consecutive objects of one lane group
 };
 
-inline int sagg_width(int64_t items, int64_t rows) {
-  const int64_t mean = rows > 0 ? (items + rows - 1) / rows : 0;
-  const int64_t want = (mean + 7) / 8;
-  int w = 1;
-  while (w < 64 && w < want) w <<= 1;
-  return w;
-}
-
-inline int32_t sagg_grid(int64_t rows, int width, int n_cu) {
-  // no LDS on the group path: 8 blocks (32 waves) a CU, each lane group striding
-  const int64_t per_block = 256 / width, want = (rows + per_block - 1) / per_block, cap = (int64_t)n_cu * 8;
-  return (int32_t)(want < cap ? want : cap);
-}
-
 inline SaggRoute route_sagg(int O, int n_long, int64_t short_segments, int n_cu) {
   SaggRoute r{};
   const int n_short = O - n_long;
-  r.width = sagg_width(short_segments, n_short);
+  r.width = group_width(short_segments, n_short, 1, 8);
   r.long_min = SAGG_LONG_MIN;
   r.threads = 256;
-  // the groups stride over all O objects and skip the long ones
-  r.grid = n_short > 0 ? sagg_grid(O, r.width, n_cu) : 0;
+  // the groups stride over all O objects and skip the long ones; no LDS on the group path
+  r.grid = n_short > 0 ? group_grid(O, r.width, n_cu) : 0;
   r.long_grid = n_long;
-  r.stride = r.grid * (256 / r.width);
+  r.stride = group_stride(r.grid, r.width);
   return r;
 }
 

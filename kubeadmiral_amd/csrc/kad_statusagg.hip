@@ -248,15 +248,9 @@ __global__ __launch_bounds__(256) void sagg_kernel(SaggDev d) {
 
 template <int KIND>
 static void launch_kind(const SaggDev& d, int width, unsigned grid, hipStream_t st) {
-  switch (width) {
-    case 1: hipLaunchKernelGGL((sagg_kernel<1, KIND>), dim3(grid), dim3(256), 0, st, d); break;
-    case 2: hipLaunchKernelGGL((sagg_kernel<2, KIND>), dim3(grid), dim3(256), 0, st, d); break;
-    case 4: hipLaunchKernelGGL((sagg_kernel<4, KIND>), dim3(grid), dim3(256), 0, st, d); break;
-    case 8: hipLaunchKernelGGL((sagg_kernel<8, KIND>), dim3(grid), dim3(256), 0, st, d); break;
-    case 16: hipLaunchKernelGGL((sagg_kernel<16, KIND>), dim3(grid), dim3(256), 0, st, d); break;
-    case 32: hipLaunchKernelGGL((sagg_kernel<32, KIND>), dim3(grid), dim3(256), 0, st, d); break;
-    default: hipLaunchKernelGGL((sagg_kernel<64, KIND>), dim3(grid), dim3(256), 0, st, d); break;
-  }
+  with_width<1>(width, [&](auto W) {
+    hipLaunchKernelGGL((sagg_kernel<decltype(W)::value, KIND>), dim3(grid), dim3(256), 0, st, d);
+  });
 }
 
 hipError_t launch_sagg(int kind, const SaggDev& d, const SaggRoute& r, hipStream_t st) {
@@ -286,8 +280,6 @@ struct SaggPlan {
   std::vector<int32_t> long_list;
   int64_t short_segments = 0;
 };
-
-bool sagg_width_ok(int w) { return w == 0 || (w >= 1 && w <= 64 && (w & (w - 1)) == 0); }
 
 }  // namespace
 
@@ -358,7 +350,8 @@ static int validate_sagg(const kad_sagg_batch* b, const kad_sagg_view* out, int 
 }
 
 static int status_aggregate_locked(kad_ctx* c, const kad_sagg_batch* b, const kad_sagg_view* out) {
-  const int long_min = c->sagg_force_long_min > 0 ? c->sagg_force_long_min : SAGG_LONG_MIN;
+  Stage& stg = c->stage[STG_SAGG];
+  const int long_min = stg.force.long_min_or(SAGG_LONG_MIN);
   std::string err;
   SaggPlan plan;
   if (int r = validate_sagg(b, out, long_min, &plan, &err)) return fail(c, r, err);
@@ -368,79 +361,65 @@ static int status_aggregate_locked(kad_ctx* c, const kad_sagg_batch* b, const ka
   const bool dep = b->kind == KAD_SAGG_DEPLOYMENT;
   const int n_long = (int)plan.long_list.size();
   SaggRoute route = route_sagg(O, n_long, plan.short_segments, n_cus());
-  if (c->sagg_force_width > 0 && n_long < O) {
-    route.width = c->sagg_force_width;
-    route.grid = sagg_grid(O, route.width, n_cus());
-    route.stride = route.grid * (256 / route.width);
-  }
+  group_force_apply(stg.force, n_long < O, O, n_cus(), route.width, route.grid, &route.stride);
   route.long_min = long_min;
-  // one buffer: the inputs, then the outputs
+  // one buffer: the inputs, then the outputs (the other kind's arrays are absent)
   const size_t o = (size_t)O, sg = (size_t)S, nl = (size_t)n_long;
   const size_t nv = dep ? SAGG_NV_DEP : SAGG_NV_JOB, nold = dep ? SAGG_NOLD_DEP : SAGG_NOLD_JOB;
-  Arena a;
-  const Part p_so = a.in(b->obj_seg_off, 4 * (o + 1)), p_of = a.in(b->obj_flags, o),
-             p_og = dep ? a.in(b->obj_generation, 8 * o) : Arena::absent(),
-             p_oo = dep ? a.in(b->obj_observed, 8 * o) : Arena::absent(), p_ov = a.in(b->old_vals, 8 * nold * o),
-             p_sv = a.in(b->seg_vals, 4 * nv * sg), p_sf = a.in(b->seg_flags, sg),
-             p_sa = a.in(dep ? b->seg_observed : b->seg_start, 8 * sg), p_sb = a.in(dep ? b->seg_synced : b->seg_done, 8 * sg),
-             p_ol = a.in(plan.obj_long.data(), o), p_ll = a.in(plan.long_list.data(), 4 * nl);
-  const Part o_sums = a.out(4 * nv * o), o_changed = a.out(o), o_obs = dep ? a.out(8 * o) : Arena::absent(),
-             o_start = dep ? Arena::absent() : a.out(8 * o), o_done = dep ? Arena::absent() : a.out(8 * o),
-             o_nd = dep ? Arena::absent() : a.out(4 * o), o_nf = dep ? Arena::absent() : a.out(4 * o),
-             o_fin = dep ? Arena::absent() : a.out(o);
-  Stage& stg = c->stage[STG_SAGG];
-  if (int r = a.commit(c, stg.buf)) return r;
   SaggDev d{};
   d.O = O;
   d.S = S;
   d.n_long = n_long;
-  d.obj_seg_off = a.ptr<const int32_t>(stg.buf, p_so);
-  d.obj_flags = a.ptr<const uint8_t>(stg.buf, p_of);
-  d.obj_generation = a.ptr<const int64_t>(stg.buf, p_og);
-  d.obj_observed = a.ptr<const int64_t>(stg.buf, p_oo);
-  d.old_vals = a.ptr<const int64_t>(stg.buf, p_ov);
-  d.seg_vals = a.ptr<const int32_t>(stg.buf, p_sv);
-  d.seg_flags = a.ptr<const uint8_t>(stg.buf, p_sf);
-  d.seg_a = a.ptr<const int64_t>(stg.buf, p_sa);
-  d.seg_b = a.ptr<const int64_t>(stg.buf, p_sb);
-  d.obj_long = a.ptr<const uint8_t>(stg.buf, p_ol);
-  d.long_list = a.ptr<const int32_t>(stg.buf, p_ll);
-  d.sums = a.ptr<int32_t>(stg.buf, o_sums);
-  d.changed = a.ptr<uint8_t>(stg.buf, o_changed);
-  d.observed = a.ptr<int64_t>(stg.buf, o_obs);
-  d.start_min = a.ptr<int64_t>(stg.buf, o_start);
-  d.done_max = a.ptr<int64_t>(stg.buf, o_done);
-  d.n_done = a.ptr<int32_t>(stg.buf, o_nd);
-  d.n_failed = a.ptr<int32_t>(stg.buf, o_nf);
-  d.finished = a.ptr<uint8_t>(stg.buf, o_fin);
+  Arena a;
+  a.in(d.obj_seg_off, b->obj_seg_off, o + 1);
+  a.in(d.obj_flags, b->obj_flags, o);
+  if (dep) {
+    a.in(d.obj_generation, b->obj_generation, o);
+    a.in(d.obj_observed, b->obj_observed, o);
+  } else {
+    a.absent(d.obj_generation);
+    a.absent(d.obj_observed);
+  }
+  a.in(d.old_vals, b->old_vals, nold * o);
+  a.in(d.seg_vals, b->seg_vals, nv * sg);
+  a.in(d.seg_flags, b->seg_flags, sg);
+  a.in(d.seg_a, dep ? b->seg_observed : b->seg_start, sg);
+  a.in(d.seg_b, dep ? b->seg_synced : b->seg_done, sg);
+  a.in(d.obj_long, plan.obj_long.data(), o);
+  a.in(d.long_list, plan.long_list.data(), nl);
+  a.out(d.sums, out->sums, nv * o);
+  a.out(d.changed, out->changed, o);
+  if (dep) {
+    a.out(d.observed, out->observed, o);
+    a.absent(d.start_min);
+    a.absent(d.done_max);
+    a.absent(d.n_done);
+    a.absent(d.n_failed);
+    a.absent(d.finished);
+  } else {
+    a.absent(d.observed);
+    a.out(d.start_min, out->start_min, o);
+    a.out(d.done_max, out->done_max, o);
+    a.out(d.n_done, out->n_done, o);
+    a.out(d.n_failed, out->n_failed, o);
+    a.out(d.finished, out->finished, o);
+  }
+  if (int r = a.commit(c, stg.buf)) return r;
   HIPCHK(c, hipEventRecord(stg.ev[0], c->stream));
   HIPCHK(c, launch_sagg(b->kind, d, route, c->stream));
   HIPCHK(c, hipEventRecord(stg.ev[1], c->stream));
-  stg.ran = true;
-  c->sagg_route = route;
-  HIPCHK(c, hipMemcpyAsync(out->sums, d.sums, 4 * nv * o, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(out->changed, d.changed, o, hipMemcpyDeviceToHost, c->stream));
-  if (dep) {
-    HIPCHK(c, hipMemcpyAsync(out->observed, d.observed, 8 * o, hipMemcpyDeviceToHost, c->stream));
-  } else {
-    HIPCHK(c, hipMemcpyAsync(out->start_min, d.start_min, 8 * o, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(out->done_max, d.done_max, 8 * o, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(out->n_done, d.n_done, 4 * o, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(out->n_failed, d.n_failed, 4 * o, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(out->finished, d.finished, o, hipMemcpyDeviceToHost, c->stream));
-  }
+  stage_ran(stg, route);
+  if (int r = a.fetch(c)) return r;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return KAD_OK;
 }
 
 int kad_sagg_check(const kad_sagg_batch* b, const kad_sagg_view* out) {
-  try {
+  return check_guarded([&]() -> int {
     if (!b) return KAD_EINVAL;
     std::string err;
     return validate_sagg(b, out, SAGG_LONG_MIN, nullptr, &err);
-  } catch (...) {
-    return KAD_EHOST;
-  }
+  });
 }
 
 int kad_status_aggregate(kad_ctx* c, const kad_sagg_batch* b, const kad_sagg_view* out) {
@@ -449,32 +428,17 @@ int kad_status_aggregate(kad_ctx* c, const kad_sagg_batch* b, const kad_sagg_vie
   });
 }
 
-int kad_sagg_timing(kad_ctx* c, float ms[1]) {
-  return entry(c, ms != nullptr, [&] { return stage_timing(c, c->stage[STG_SAGG], 1, ms, "no kad_status_aggregate ran"); });
-}
+int kad_sagg_timing(kad_ctx* c, float ms[1]) { return stage_timing(c, STG_SAGG, 1, ms, "no kad_status_aggregate ran"); }
 
 int kad_sagg_route_eval(int32_t n_objects, int32_t n_long, int64_t short_segments, int32_t n_cu, int32_t* out) {
   if (!out || n_objects < 0 || n_long < 0 || n_long > n_objects || short_segments < 0 || n_cu < 1) return KAD_EINVAL;
-  const SaggRoute r = route_sagg(n_objects, n_long, short_segments, n_cu);
-  static_assert(sizeof r == 4 * KAD_SAGG_ROUTE_FIELDS, "kad_sagg_route_eval's record");
-  memcpy(out, &r, sizeof r);
-  return KAD_OK;
+  return route_record<KAD_SAGG_ROUTE_FIELDS>(out, route_sagg(n_objects, n_long, short_segments, n_cu));
 }
 
-int kad_sagg_last_route(kad_ctx* c, int32_t* out) {
-  return entry(c, out != nullptr, [&]() -> int {
-    if (!c->stage[STG_SAGG].ran) return fail(c, KAD_ESTATE, "no kad_status_aggregate ran");
-    memcpy(out, &c->sagg_route, sizeof c->sagg_route);
-    return KAD_OK;
-  });
-}
+int kad_sagg_last_route(kad_ctx* c, int32_t* out) { return stage_last_route(c, STG_SAGG, out, "no kad_status_aggregate ran"); }
 
 int kad_sagg_debug_route(kad_ctx* c, int32_t force_width, int32_t force_long_min) {
-  return entry(c, force_long_min >= 0 && sagg_width_ok(force_width), [&]() -> int {
-    c->sagg_force_width = force_width;
-    c->sagg_force_long_min = force_long_min;
-    return KAD_OK;
-  });
+  return stage_debug_route(c, STG_SAGG, group_width_ok(force_width, 1), GroupForce{force_width, force_long_min, 0});
 }
 
 }  // extern "C"

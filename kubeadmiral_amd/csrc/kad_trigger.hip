@@ -198,17 +198,16 @@ static int trigger_prefixes_upload_locked(kad_ctx* c, int n, const int64_t* pref
   HIPCHK(c, hipSetDevice(c->device));
   const size_t nbytes = (size_t)prefix_off[n];
   if (int r = grow(c, c->t_prefix, nbytes + 64)) return r;
+  TriggerDev& t = c->td;
   Arena a;
-  const Part p_off = a.in(prefix_off, 8 * ((size_t)n + 1)), o_out = a.out(4 * (size_t)n);
+  a.in(t.prefix_off, prefix_off, (size_t)n + 1);
+  a.out(t.out, (size_t)n);  // kad_trigger_download copies it, after a run
   Stage& stg = c->stage[STG_TRIGGER];
   if (int r = a.commit(c, stg.buf)) return r;
   if (nbytes) HIPCHK(c, hipMemcpyAsync(c->t_prefix.p, prefix, nbytes, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  TriggerDev& t = c->td;
   t.n = n;
   t.prefix = c->t_prefix.as<const uint8_t>();
-  t.prefix_off = a.ptr<const int64_t>(stg.buf, p_off);
-  t.out = a.ptr<uint32_t>(stg.buf, o_out);
   c->t_n = n;
   stg.ran = false;
   return KAD_OK;

@@ -195,6 +195,20 @@ def route_eval(per_cu: int = 1, row_per_cu: int = 1, **inputs) -> dict:
     return _route_dict(L, out)
 
 
+_I32, _I64 = ctypes.c_int32, ctypes.c_int64
+# The consumer calls' ABI by call name: the call itself, then the arguments that follow (batch, view) in
+# kad_<name>_check, the inputs of kad_<name>_route_eval, and those of kad_<name>_debug_route (None: it has none).
+# kad_<name>_timing and kad_<name>_last_route take (ctx, out).
+_CONSUMER_ABI = {
+    "follower": ("kad_follower_union", (_I32, _I32), (_I32, _I32, _I32), None),
+    "migrate": ("kad_migrate_estimate", (_I32,), (_I32, _I64, _I32, _I32, _I32), (_I32, _I32)),
+    "cstat": ("kad_cluster_resources", (), (_I32, _I32, _I64, _I64, _I32, _I32), (_I32, _I32)),
+    "sagg": ("kad_status_aggregate", (), (_I32, _I32, _I64, _I32), (_I32, _I32)),
+    "rollout": ("kad_rollout_plan", (ctypes.c_void_p,), (_I32, _I32, _I64, _I32, _I32), (_I32, _I32, _I32)),
+    "dispatch": ("kad_dispatch_plan", (), (_I32, _I32, _I32), None),
+}
+
+
 def load_library(path: str = LIB_PATH):
     """Load libkad.so (fails loudly: the product path has no CPU fallback)."""
     global _lib
@@ -241,50 +255,18 @@ def load_library(path: str = LIB_PATH):
         L.kad_override_policies_check.argtypes = [P, SZ, P, SZ]
         L.kad_override_match.argtypes = [P, P, P]
         L.kad_override_timing.argtypes = [P, P]
-    if hasattr(L, "kad_follower_union"):
-        L.kad_follower_union.argtypes = [P, P, P]
-        L.kad_follower_check.argtypes = [P, P, ctypes.c_int32, ctypes.c_int32]
-        L.kad_follower_timing.argtypes = [P, P]
-        L.kad_follower_route_eval.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, P]
-        L.kad_follower_last_route.argtypes = [P, P]
-    if hasattr(L, "kad_migrate_estimate"):
-        L.kad_migrate_estimate.argtypes = [P, P, P]
-        L.kad_migrate_check.argtypes = [P, P, ctypes.c_int32]
-        L.kad_migrate_timing.argtypes = [P, P]
-        L.kad_migrate_route_eval.argtypes = [ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
-                                             ctypes.c_int32, P]
-        L.kad_migrate_last_route.argtypes = [P, P]
-        L.kad_migrate_debug_route.argtypes = [P, ctypes.c_int32, ctypes.c_int32]
-    if hasattr(L, "kad_cluster_resources"):
-        L.kad_cluster_resources.argtypes = [P, P, P]
-        L.kad_cstat_check.argtypes = [P, P]
-        L.kad_cstat_timing.argtypes = [P, P]
-        L.kad_cstat_route_eval.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64,
-                                           ctypes.c_int32, ctypes.c_int32, P]
-        L.kad_cstat_last_route.argtypes = [P, P]
-        L.kad_cstat_debug_route.argtypes = [P, ctypes.c_int32, ctypes.c_int32]
-    if hasattr(L, "kad_status_aggregate"):
-        L.kad_status_aggregate.argtypes = [P, P, P]
-        L.kad_sagg_check.argtypes = [P, P]
-        L.kad_sagg_timing.argtypes = [P, P]
-        L.kad_sagg_route_eval.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, P]
-        L.kad_sagg_last_route.argtypes = [P, P]
-        L.kad_sagg_debug_route.argtypes = [P, ctypes.c_int32, ctypes.c_int32]
-    if hasattr(L, "kad_rollout_plan"):
-        L.kad_rollout_plan.argtypes = [P, P, P]
-        L.kad_rollout_check.argtypes = [P, P, P]
-        L.kad_rollout_timing.argtypes = [P, P]
-        L.kad_rollout_route_eval.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32,
-                                             ctypes.c_int32, P]
-        L.kad_rollout_last_route.argtypes = [P, P]
-        L.kad_rollout_debug_route.argtypes = [P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
-    if hasattr(L, "kad_dispatch_plan"):
-        L.kad_dispatch_plan.argtypes = [P, P, P]
-        L.kad_dispatch_check.argtypes = [P, P]
+    for name, (main, check, route_in, force) in _CONSUMER_ABI.items():
+        if not hasattr(L, main):  # (absent from libraries of older revisions: A/B runs)
+            continue
+        getattr(L, main).argtypes = [P, P, P]
+        getattr(L, f"kad_{name}_check").argtypes = [P, P, *check]
+        getattr(L, f"kad_{name}_timing").argtypes = [P, P]
+        getattr(L, f"kad_{name}_route_eval").argtypes = [*route_in, P]
+        getattr(L, f"kad_{name}_last_route").argtypes = [P, P]
+        if force is not None:
+            getattr(L, f"kad_{name}_debug_route").argtypes = [P, *force]
+    if hasattr(L, "kad_dispatch_decide"):
         L.kad_dispatch_decide.argtypes = [ctypes.c_uint32, ctypes.c_int32, ctypes.c_uint32, ctypes.c_uint32, P]
-        L.kad_dispatch_timing.argtypes = [P, P]
-        L.kad_dispatch_route_eval.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, P]
-        L.kad_dispatch_last_route.argtypes = [P, P]
     L.kad_debug_inject_fault.argtypes = [P, I]
     L.kad_debug_plan_force_workspace.argtypes = [P, I]
     L.kad_trigger_suffix_upload.argtypes = [P, P, SZ]
@@ -356,22 +338,51 @@ def _p(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
+# ---- the consumer calls' table-driven halves: every *_route_eval, *_args and *_check below is one line over these
+def _route_eval(name: str, fields, *args, error=None) -> dict:
+    """kad_<name>_route_eval on ``args``: the record as a dict of ``fields``."""
+    fn = f"kad_{name}_route_eval"
+    out = (ctypes.c_int32 * len(fields))()
+    rc = getattr(load_library(), fn)(*args, out)
+    if rc != 0:
+        raise ValueError(f"{fn}: {rc}") if error is None else error(rc, fn)
+    return dict(zip(fields, out))
+
+
+def _flat(table, arrays, required=False) -> dict:
+    """The arrays of ``table``'s rows (name, dtype, ...) as contiguous 1-d arrays of their dtype."""
+    return {k: np.ascontiguousarray(arrays[k], dt).reshape(-1) for k, dt, *_ in table if required or k in arrays}
+
+
+def _call_args(batch_cls, view_cls, counts, ins, outs, a: dict, n: dict):
+    """(batch, view, the input arrays, the output arrays by name) of one consumer call. ``counts`` lead the batch,
+    then one pointer per row of ``ins`` (null for an array that ``a`` lacks or that is empty). An output of ``outs``
+    has n[its name] elements, else n[its third column], and is allocated with one at least; one with neither is
+    left null."""
+    size = {k: n.get(k, n.get(dim)) for k, _, dim in outs}
+    out = {k: np.zeros(max(1, size[k]), dt) for k, dt, _ in outs if size[k] is not None}
+    b = batch_cls(*counts, *(a[k].ctypes.data if k in a and len(a[k]) else None for k, *_ in ins))
+    v = view_cls(*(out[k].ctypes.data if k in out else None for k, _, _ in outs))
+    return b, v, a, {k: o[:size[k]] for k, o in out.items()}
+
+
+def _check(name: str, args, *extra) -> int:
+    """kad_<name>_check on the (batch, view, ...) of an *_args function."""
+    b, v = args[:2]
+    return getattr(load_library(), f"kad_{name}_check")(ctypes.byref(b), ctypes.byref(v), *extra)
+
+
 FOLLOWER_ROUTE = ("path", "words", "threads", "grid", "lds", "stride")  # kad_follower_route_eval's record
 
 
-def _follower_route_dict(out) -> dict:
-    d = dict(zip(FOLLOWER_ROUTE, out))
+def _follower_route_dict(d: dict) -> dict:
     d["path"] = ("WAVE", "BLOCK")[d["path"]]
     return d
 
 
 def follower_route_eval(n_ids: int, n_followers: int, n_cu: int = 256) -> dict:
     """kad_follower_route_eval: the launch decision of a follower_union (needs no GPU)."""
-    out = (ctypes.c_int32 * len(FOLLOWER_ROUTE))()
-    rc = load_library().kad_follower_route_eval(n_ids, n_followers, n_cu, out)
-    if rc != 0:
-        raise ValueError(f"kad_follower_route_eval: {rc}")
-    return _follower_route_dict(out)
+    return _follower_route_dict(_route_eval("follower", FOLLOWER_ROUTE, n_ids, n_followers, n_cu))
 
 
 def follower_args(n_ids: int, followers, leaders=None, keep=None, sched=None, n_leaders=None,
@@ -408,8 +419,7 @@ def follower_args(n_ids: int, followers, leaders=None, keep=None, sched=None, n_
 def follower_check(n_clusters: int, n_units: int, n_ids: int, followers, **kw) -> int:
     """kad_follower_check: kad_follower_union's validation of :func:`follower_args` arguments against a snapshot
     of ``n_clusters`` clusters and a scheduled batch of ``n_units`` units (-1: none); no GPU. Returns the code."""
-    b, v, _keepalive, _ = follower_args(n_ids, followers, **kw)
-    return load_library().kad_follower_check(ctypes.byref(b), ctypes.byref(v), n_clusters, n_units)
+    return _check("follower", follower_args(n_ids, followers, **kw), n_clusters, n_units)
 
 
 MIGRATE_ROUTE = ("width", "long_min", "threads", "grid", "long_grid", "stride", "obj_width", "obj_grid")
@@ -417,11 +427,7 @@ MIGRATE_ROUTE = ("width", "long_min", "threads", "grid", "long_grid", "stride", 
 
 def migrate_route_eval(n_segments: int, n_pods: int, n_long: int, n_objects: int, n_cu: int = 256) -> dict:
     """kad_migrate_route_eval: the launch decision of a migrate_estimate (needs no GPU)."""
-    out = (ctypes.c_int32 * len(MIGRATE_ROUTE))()
-    rc = load_library().kad_migrate_route_eval(n_segments, n_pods, n_long, n_objects, n_cu, out)
-    if rc != 0:
-        raise ValueError(f"kad_migrate_route_eval: {rc}")
-    return dict(zip(MIGRATE_ROUTE, out))
+    return _route_eval("migrate", MIGRATE_ROUTE, n_segments, n_pods, n_long, n_objects, n_cu)
 
 
 _MIGRATE_IN = (("obj_seg_off", np.int32), ("obj_threshold_ns", np.int64), ("seg_cluster", np.int32),
@@ -435,21 +441,16 @@ def migrate_args(n_ids: int, now_ns: int, **arrays):
     """The kad_migrate_batch / kad_migrate_view of one call with the arrays that back them (the batch's
     fields by name; the counts are taken from the arrays as they are, so that a malformed batch reaches the
     library's validation). Returns (batch, view, the input arrays, the output arrays by name)."""
-    a = {k: np.ascontiguousarray(arrays[k], dt).reshape(-1) for k, dt in _MIGRATE_IN}
+    a = _flat(_MIGRATE_IN, arrays, required=True)
     O_, S_ = len(a["obj_threshold_ns"]), len(a["seg_cluster"])
-    n = {"O": O_, "S": S_}
-    out = {k: np.zeros(max(1, n[dim]), dt) for k, dt, dim in _MIGRATE_OUT}
-    b = MigrateBatch(int(n_ids), O_, S_, len(a["old_cluster"]), len(a["pod_t_ns"]), int(now_ns),
-                     *(a[k].ctypes.data if len(a[k]) else None for k, _ in _MIGRATE_IN))
-    v = MigrateView(*(out[k].ctypes.data for k, _, _ in _MIGRATE_OUT))
-    return b, v, a, {k: out[k][:n[dim]] for k, _, dim in _MIGRATE_OUT}
+    counts = (int(n_ids), O_, S_, len(a["old_cluster"]), len(a["pod_t_ns"]), int(now_ns))
+    return _call_args(MigrateBatch, MigrateView, counts, _MIGRATE_IN, _MIGRATE_OUT, a, {"O": O_, "S": S_})
 
 
 def migrate_check(n_clusters: int, n_ids: int, now_ns: int, **arrays) -> int:
     """kad_migrate_check: kad_migrate_estimate's validation of :func:`migrate_args` arguments against a
     snapshot of ``n_clusters`` clusters; no GPU. Returns the code."""
-    b, v, _keepalive, _ = migrate_args(n_ids, now_ns, **arrays)
-    return load_library().kad_migrate_check(ctypes.byref(b), ctypes.byref(v), n_clusters)
+    return _check("migrate", migrate_args(n_ids, now_ns, **arrays), n_clusters)
 
 
 CSTAT_ROUTE = ("node_width", "pod_width", "long_min", "threads", "node_grid", "pod_grid", "long_grid", "chunk_grid")
@@ -458,11 +459,7 @@ CSTAT_ROUTE = ("node_width", "pod_width", "long_min", "threads", "node_grid", "p
 def cstat_route_eval(n_clusters: int, n_long: int, short_nodes: int, short_pods: int, n_chunks: int,
                      n_cu: int = 256) -> dict:
     """kad_cstat_route_eval: the launch decision of a cluster_resources (needs no GPU)."""
-    out = (ctypes.c_int32 * len(CSTAT_ROUTE))()
-    rc = load_library().kad_cstat_route_eval(n_clusters, n_long, short_nodes, short_pods, n_chunks, n_cu, out)
-    if rc != 0:
-        raise ValueError(f"kad_cstat_route_eval: {rc}")
-    return dict(zip(CSTAT_ROUTE, out))
+    return _route_eval("cstat", CSTAT_ROUTE, n_clusters, n_long, short_nodes, short_pods, n_chunks, n_cu)
 
 
 _CSTAT_IN = (("cl_node_off", np.int64), ("node_flags", np.uint8), ("node_ent_off", np.int64), ("nent_res", np.uint8),
@@ -475,21 +472,16 @@ def cstat_args(n_res: int, **arrays):
     """The kad_cstat_batch / kad_cstat_view of one call with the arrays that back them (the batch's fields by
     name; the counts are taken from the arrays as they are, so that a malformed batch reaches the library's
     validation). Returns (batch, view, the input arrays, the output arrays by name)."""
-    a = {k: np.ascontiguousarray(arrays[k], dt).reshape(-1) for k, dt in _CSTAT_IN}
+    a = _flat(_CSTAT_IN, arrays, required=True)
     K = max(0, len(a["cl_node_off"]) - 1)
-    n = {"K": K, "KR": K * max(0, int(n_res))}
-    out = {k: np.zeros(max(1, n[dim]), dt) for k, dt, dim in _CSTAT_OUT}
-    b = CstatBatch(K, int(n_res), len(a["node_flags"]), len(a["pod_flags"]), len(a["nent_val"]), len(a["pent_val"]),
-                   *(a[k].ctypes.data if len(a[k]) else None for k, _ in _CSTAT_IN))
-    v = CstatView(*(out[k].ctypes.data for k, _, _ in _CSTAT_OUT))
-    return b, v, a, {k: out[k][:n[dim]] for k, _, dim in _CSTAT_OUT}
+    counts = (K, int(n_res), len(a["node_flags"]), len(a["pod_flags"]), len(a["nent_val"]), len(a["pent_val"]))
+    return _call_args(CstatBatch, CstatView, counts, _CSTAT_IN, _CSTAT_OUT, a, {"K": K, "KR": K * max(0, int(n_res))})
 
 
 def cstat_check(n_res: int, **arrays) -> int:
     """kad_cstat_check: kad_cluster_resources' validation of :func:`cstat_args` arguments; no GPU. Returns the
     code."""
-    b, v, _keepalive, _ = cstat_args(n_res, **arrays)
-    return load_library().kad_cstat_check(ctypes.byref(b), ctypes.byref(v))
+    return _check("cstat", cstat_args(n_res, **arrays))
 
 
 SAGG_ROUTE = ("width", "long_min", "threads", "grid", "long_grid", "stride")
@@ -500,13 +492,10 @@ SAGG_NOLD = {SAGG_DEPLOYMENT: 6, SAGG_JOB: 5}  # int64 rows of old_vals
 
 def sagg_route_eval(n_objects: int, n_long: int, short_segments: int, n_cu: int = 256) -> dict:
     """kad_sagg_route_eval: the launch decision of a status_aggregate (needs no GPU)."""
-    out = (ctypes.c_int32 * len(SAGG_ROUTE))()
-    rc = load_library().kad_sagg_route_eval(n_objects, n_long, short_segments, n_cu, out)
-    if rc != 0:
-        raise ValueError(f"kad_sagg_route_eval: {rc}")
-    return dict(zip(SAGG_ROUTE, out))
+    return _route_eval("sagg", SAGG_ROUTE, n_objects, n_long, short_segments, n_cu)
 
 
+# (name, dtype, the kind it belongs to: 0 Deployment, 1 Job, 2 both)
 _SAGG_IN = (("obj_seg_off", np.int32, 2), ("obj_flags", np.uint8, 2), ("obj_generation", np.int64, 0),
             ("obj_observed", np.int64, 0), ("old_vals", np.int64, 2), ("seg_vals", np.int32, 2), ("seg_flags", np.uint8, 2),
             ("seg_observed", np.int64, 0), ("seg_synced", np.int64, 0), ("seg_start", np.int64, 1), ("seg_done", np.int64, 1))
@@ -519,22 +508,20 @@ def sagg_args(kind: int, **arrays):
     the counts are taken from the arrays as they are, so that a malformed batch reaches the library's
     validation; the other kind's arrays are left null). Returns (batch, view, the input arrays, the output
     arrays by name: ``sums`` as [NV, O])."""
-    mine = lambda which: which == 2 or which == (1 if kind == SAGG_JOB else 0)  # noqa: E731
-    a = {k: np.ascontiguousarray(arrays[k], dt).reshape(-1) for k, dt, which in _SAGG_IN if mine(which) and k in arrays}
+    mine = (2, 1 if kind == SAGG_JOB else 0)
+    a = _flat([row for row in _SAGG_IN if row[2] in mine], arrays)
     O_, S_ = len(a["obj_flags"]), len(a["seg_flags"])
     nv = SAGG_NV.get(kind, 5)
-    out = {k: np.zeros(max(1, O_ * (nv if k == "sums" else 1)), dt) for k, dt, which in _SAGG_OUT if mine(which)}
-    b = SaggBatch(int(kind), O_, S_, 0, *(a[k].ctypes.data if k in a and len(a[k]) else None for k, _, _ in _SAGG_IN))
-    v = SaggView(*(out[k].ctypes.data if k in out else None for k, _, _ in _SAGG_OUT))
-    res = {k: (o[:nv * O_].reshape(nv, O_) if k == "sums" else o[:O_]) for k, o in out.items()}
+    n = {"sums": nv * O_, **{which: O_ for which in mine}}
+    b, v, a, res = _call_args(SaggBatch, SaggView, (int(kind), O_, S_, 0), _SAGG_IN, _SAGG_OUT, a, n)
+    res["sums"] = res["sums"].reshape(nv, O_)
     return b, v, a, res
 
 
 def sagg_check(kind: int, **arrays) -> int:
     """kad_sagg_check: kad_status_aggregate's validation of :func:`sagg_args` arguments; no GPU. Returns the
     code."""
-    b, v, _keepalive, _ = sagg_args(kind, **arrays)
-    return load_library().kad_sagg_check(ctypes.byref(b), ctypes.byref(v))
+    return _check("sagg", sagg_args(kind, **arrays))
 
 
 ROLLOUT_ROUTE = ("width", "long_min", "threads", "grid", "long_grid", "stride", "serial")
@@ -543,11 +530,7 @@ ROLLOUT_NV = 10  # int32 rows of tgt_vals
 
 def rollout_route_eval(n_objects: int, n_long: int, short_targets: int, n_serial: int = 0, n_cu: int = 256) -> dict:
     """kad_rollout_route_eval: the launch decision of a rollout_plan (needs no GPU)."""
-    out = (ctypes.c_int32 * len(ROLLOUT_ROUTE))()
-    rc = load_library().kad_rollout_route_eval(n_objects, n_long, short_targets, n_serial, n_cu, out)
-    if rc != 0:
-        raise ValueError(f"kad_rollout_route_eval: {rc}")
-    return dict(zip(ROLLOUT_ROUTE, out))
+    return _route_eval("rollout", ROLLOUT_ROUTE, n_objects, n_long, short_targets, n_serial, n_cu)
 
 
 _ROLLOUT_IN = (("obj_tgt_off", np.int32), ("obj_max_surge", np.int32), ("obj_max_unavailable", np.int32),
@@ -560,21 +543,18 @@ def rollout_args(**arrays):
     """The kad_rollout_batch / kad_rollout_view of one call with the arrays that back them (the batch's fields by
     name; the counts are taken from obj_flags and tgt_flags as they are, so that a malformed batch reaches the
     library's validation). Returns (batch, view, the input arrays, the output arrays by name)."""
-    a = {k: np.ascontiguousarray(arrays[k], dt).reshape(-1) for k, dt in _ROLLOUT_IN if k in arrays}
+    a = _flat(_ROLLOUT_IN, arrays)
     n = (len(a["obj_flags"]), len(a["tgt_flags"]))
-    out = {k: np.zeros(max(1, n[dim]), dt) for k, dt, dim in _ROLLOUT_OUT}
-    b = RolloutBatch(n[0], n[1], *(a[k].ctypes.data if k in a and len(a[k]) else None for k, _ in _ROLLOUT_IN))
-    v = RolloutView(*(out[k].ctypes.data for k, _, _ in _ROLLOUT_OUT))
-    return b, v, a, {k: out[k][:n[dim]] for k, _, dim in _ROLLOUT_OUT}
+    return _call_args(RolloutBatch, RolloutView, n, _ROLLOUT_IN, _ROLLOUT_OUT, a, dict(enumerate(n)))
 
 
 def rollout_check(**arrays):
     """kad_rollout_check: kad_rollout_plan's validation of :func:`rollout_args` arguments; no GPU. Returns (the code,
     nowrap[O]: the objects the device plans with prefix sums)."""
-    b, v, _keepalive, _ = rollout_args(**arrays)
-    nowrap = np.zeros(max(1, b.n_objects), np.uint8)
-    rc = load_library().kad_rollout_check(ctypes.byref(b), ctypes.byref(v), nowrap.ctypes.data)
-    return rc, nowrap[:max(0, b.n_objects)]
+    args = rollout_args(**arrays)
+    O_ = args[0].n_objects
+    nowrap = np.zeros(max(1, O_), np.uint8)
+    return _check("rollout", args, nowrap.ctypes.data), nowrap[:max(0, O_)]
 
 
 DISPATCH_ROUTE = ("words", "threads", "grid", "lds", "stride")
@@ -583,11 +563,7 @@ DISPATCH_MAX_CLUSTERS = 16384
 
 def dispatch_route_eval(n_clusters: int, n_objects: int, n_cu: int = 256) -> dict:
     """kad_dispatch_route_eval: the launch decision of a dispatch_plan (needs no GPU)."""
-    out = (ctypes.c_int32 * len(DISPATCH_ROUTE))()
-    rc = load_library().kad_dispatch_route_eval(n_clusters, n_objects, n_cu, out)
-    if rc != 0:
-        raise KadError(rc, "kad_dispatch_route_eval")
-    return dict(zip(DISPATCH_ROUTE, out))
+    return _route_eval("dispatch", DISPATCH_ROUTE, n_clusters, n_objects, n_cu, error=KadError)
 
 
 def dispatch_decide(cluster_flags: int, selected: bool, ob_flags: int = 0, obj_flags: int = 0):
@@ -611,26 +587,22 @@ def dispatch_args(fill: int = 0, **arrays):
     name; the counts are taken from cluster_flags, obj_flags and ns_pl_off as they are, so that a malformed batch
     reaches the library's validation; ``n_clusters`` overrides the first). Every byte of the three entry arrays
     starts as ``fill``. Returns (batch, view, the input arrays, the output arrays by name)."""
-    a = {k: np.ascontiguousarray(arrays[k], dt).reshape(-1) for k, dt in _DISPATCH_IN if k in arrays}
+    a = _flat(_DISPATCH_IN, arrays)
     C = int(arrays.get("n_clusters", len(a["cluster_flags"])))
     O, N = len(a["obj_flags"]), max(0, len(a["ns_pl_off"]) - 1)
     oo = a["out_off"]
     cap = int(oo[-1]) if len(oo) == O + 1 and len(oo) and 0 <= int(oo[-1]) < 2 ** 40 else 0
-    n = (O, cap)
-    out = {k: np.zeros(max(1, n[dim]), dt) for k, dt, dim in _DISPATCH_OUT}
+    b, v, a, out = _call_args(DispatchBatch, DispatchView, (C, O, N), _DISPATCH_IN, _DISPATCH_OUT, a, {0: O, 1: cap})
     if fill:
         for k, _, dim in _DISPATCH_OUT:
             if dim:
                 out[k].view(np.uint8)[:] = fill
-    b = DispatchBatch(C, O, N, *(a[k].ctypes.data if k in a and len(a[k]) else None for k, _ in _DISPATCH_IN))
-    v = DispatchView(*(out[k].ctypes.data for k, _, _ in _DISPATCH_OUT))
-    return b, v, a, {k: out[k][:n[dim]] for k, _, dim in _DISPATCH_OUT}
+    return b, v, a, out
 
 
 def dispatch_check(**arrays) -> int:
     """kad_dispatch_check: kad_dispatch_plan's validation of :func:`dispatch_args` arguments; no GPU."""
-    b, v, _keepalive, _ = dispatch_args(**arrays)
-    return load_library().kad_dispatch_check(ctypes.byref(b), ctypes.byref(v))
+    return _check("dispatch", dispatch_args(**arrays))
 
 
 class Context:
@@ -661,6 +633,28 @@ class Context:
     def _chk(self, rc):
         if rc != 0:
             raise KadError(rc, self.L.kad_last_error(self.h).decode())
+
+    # ---- the consumer calls' table-driven halves (the module's _CONSUMER_ABI names them)
+    def _consume(self, fn: str, args) -> dict:
+        """The consumer call ``fn`` on the (batch, view, inputs, outputs) of its *_args function → the outputs."""
+        b, v, _keepalive, out = args
+        self._chk(getattr(self.L, fn)(self.h, ctypes.byref(b), ctypes.byref(v)))
+        return out
+
+    def _timing(self, name: str, n: int):
+        """kad_<name>_timing: its n device intervals in ms."""
+        ms = (ctypes.c_float * n)()
+        self._chk(getattr(self.L, f"kad_{name}_timing")(self.h, ms))
+        return tuple(float(x) for x in ms)
+
+    def _last_route(self, name: str, fields) -> dict:
+        """kad_<name>_last_route: the record of kad_<name>_route_eval as a dict of ``fields``."""
+        out = (ctypes.c_int32 * len(fields))()
+        self._chk(getattr(self.L, f"kad_{name}_last_route")(self.h, out))
+        return dict(zip(fields, out))
+
+    def _debug_route(self, name: str, *force) -> None:
+        self._chk(getattr(self.L, f"kad_{name}_debug_route")(self.h, *force))
 
     def upload_snapshot(self, snap: Snapshot):
         self._chk(self.L.kad_snapshot_upload(self.h, _p(snap.blob), snap.blob.nbytes))
@@ -832,9 +826,7 @@ class Context:
 
     def explain_timing(self):
         """kad_explain_timing: device ms of the last explain() — (requirement rows, filter_explain_kernel)."""
-        ms = (ctypes.c_float * 2)()
-        self._chk(self.L.kad_explain_timing(self.h, ms))
-        return float(ms[0]), float(ms[1])
+        return self._timing("explain", 2)
 
     def upload_override_policies(self, policy_set):
         """kad_override_policies_upload: an overrides.PolicySet packed against the uploaded snapshot."""
@@ -869,9 +861,7 @@ class Context:
     def override_timing(self):
         """kad_override_timing: device ms of the last override_match() — (the policy set's requirement rows,
         override_rule_rows_kernel, the status + match kernels)."""
-        ms = (ctypes.c_float * 3)()
-        self._chk(self.L.kad_override_timing(self.h, ms))
-        return float(ms[0]), float(ms[1]), float(ms[2])
+        return self._timing("override", 3)
 
     def follower_union(self, n_ids: int, followers, leaders=None, keep=None, sched=None, n_leaders=None,
                        emit_all: bool = False, capacity: Optional[int] = None, retry: bool = True) -> dict:
@@ -899,135 +889,101 @@ class Context:
     def follower_timing(self):
         """kad_follower_timing: device ms of the last follower_union() — (the union / compare kernel, the offset
         scan + the emit kernel)."""
-        ms = (ctypes.c_float * 2)()
-        self._chk(self.L.kad_follower_timing(self.h, ms))
-        return float(ms[0]), float(ms[1])
+        return self._timing("follower", 2)
 
     def follower_last_route(self) -> dict:
         """kad_follower_last_route: what the last follower_union() launched (follower_route_eval's record)."""
-        out = (ctypes.c_int32 * len(FOLLOWER_ROUTE))()
-        self._chk(self.L.kad_follower_last_route(self.h, out))
-        return _follower_route_dict(out)
+        return _follower_route_dict(self._last_route("follower", FOLLOWER_ROUTE))
 
     def migrate_estimate(self, n_ids: int, now_ns: int, **arrays) -> dict:
         """kad_migrate_estimate → {uns[S], next_cross[S], cap[S], changed[O], n_written[O], retry_after[O],
         backoff[O]}. Arguments as :func:`migrate_args` (automigration.MigrationBatch.arrays())."""
-        b, v, _keepalive, out = migrate_args(n_ids, now_ns, **arrays)
-        self._chk(self.L.kad_migrate_estimate(self.h, ctypes.byref(b), ctypes.byref(v)))
-        return out
+        return self._consume("kad_migrate_estimate", migrate_args(n_ids, now_ns, **arrays))
 
     def migrate_timing(self):
         """kad_migrate_timing: device ms of the last migrate_estimate() — (migrate_segment_kernel,
         migrate_object_kernel)."""
-        ms = (ctypes.c_float * 2)()
-        self._chk(self.L.kad_migrate_timing(self.h, ms))
-        return float(ms[0]), float(ms[1])
+        return self._timing("migrate", 2)
 
     def migrate_last_route(self) -> dict:
         """kad_migrate_last_route: what the last migrate_estimate() launched (migrate_route_eval's record)."""
-        out = (ctypes.c_int32 * len(MIGRATE_ROUTE))()
-        self._chk(self.L.kad_migrate_last_route(self.h, out))
-        return dict(zip(MIGRATE_ROUTE, out))
+        return self._last_route("migrate", MIGRATE_ROUTE)
 
     def migrate_debug_route(self, width: int = 0, long_min: int = 0) -> None:
         """kad_migrate_debug_route: the group width / long_min of the following migrate_estimate() calls
         (0: the route's own). Measurement only."""
-        self._chk(self.L.kad_migrate_debug_route(self.h, width, long_min))
+        self._debug_route("migrate", width, long_min)
 
     def cluster_resources(self, n_res: int, **arrays) -> dict:
         """kad_cluster_resources → {alloc[K * R], avail[K * R], has[K], sched_nodes[K]}. Arguments as
         :func:`cstat_args` (clusterstatus.ClusterStatusBatch.arrays())."""
-        b, v, _keepalive, out = cstat_args(n_res, **arrays)
-        self._chk(self.L.kad_cluster_resources(self.h, ctypes.byref(b), ctypes.byref(v)))
-        return out
+        return self._consume("kad_cluster_resources", cstat_args(n_res, **arrays))
 
     def cstat_timing(self):
         """kad_cstat_timing: device ms of the last cluster_resources() — (cstat_node_kernel, cstat_pod_kernel +
         cstat_combine_kernel)."""
-        ms = (ctypes.c_float * 2)()
-        self._chk(self.L.kad_cstat_timing(self.h, ms))
-        return float(ms[0]), float(ms[1])
+        return self._timing("cstat", 2)
 
     def cstat_last_route(self) -> dict:
         """kad_cstat_last_route: what the last cluster_resources() launched (cstat_route_eval's record)."""
-        out = (ctypes.c_int32 * len(CSTAT_ROUTE))()
-        self._chk(self.L.kad_cstat_last_route(self.h, out))
-        return dict(zip(CSTAT_ROUTE, out))
+        return self._last_route("cstat", CSTAT_ROUTE)
 
     def cstat_debug_route(self, width: int = 0, long_min: int = 0) -> None:
         """kad_cstat_debug_route: the group width / long_min of the following cluster_resources() calls (0: the
         route's own). Measurement only."""
-        self._chk(self.L.kad_cstat_debug_route(self.h, width, long_min))
+        self._debug_route("cstat", width, long_min)
 
     def status_aggregate(self, kind: int, **arrays) -> dict:
         """kad_status_aggregate → {sums[NV, O], changed[O]} and, Deployment, {observed[O]} or, Job, {start_min[O],
         done_max[O], n_done[O], n_failed[O], finished[O]}. Arguments as :func:`sagg_args`
         (statusagg.StatusAggBatch.arrays())."""
-        b, v, _keepalive, out = sagg_args(kind, **arrays)
-        self._chk(self.L.kad_status_aggregate(self.h, ctypes.byref(b), ctypes.byref(v)))
-        return out
+        return self._consume("kad_status_aggregate", sagg_args(kind, **arrays))
 
     def sagg_timing(self):
         """kad_sagg_timing: device ms of the last status_aggregate() — (sagg_kernel,)."""
-        ms = (ctypes.c_float * 1)()
-        self._chk(self.L.kad_sagg_timing(self.h, ms))
-        return (float(ms[0]),)
+        return self._timing("sagg", 1)
 
     def sagg_last_route(self) -> dict:
         """kad_sagg_last_route: what the last status_aggregate() launched (sagg_route_eval's record)."""
-        out = (ctypes.c_int32 * len(SAGG_ROUTE))()
-        self._chk(self.L.kad_sagg_last_route(self.h, out))
-        return dict(zip(SAGG_ROUTE, out))
+        return self._last_route("sagg", SAGG_ROUTE)
 
     def sagg_debug_route(self, width: int = 0, long_min: int = 0) -> None:
         """kad_sagg_debug_route: the group width / long_min of the following status_aggregate() calls (0: the
         route's own). Measurement only."""
-        self._chk(self.L.kad_sagg_debug_route(self.h, width, long_min))
+        self._debug_route("sagg", width, long_min)
 
     def rollout_plan(self, **arrays) -> dict:
         """kad_rollout_plan → {replicas[T], max_surge[T], max_unavailable[T], plan_flags[T], action[T], status[O]}.
         Arguments as :func:`rollout_args` (rollout.RolloutBatch.arrays())."""
-        b, v, _keepalive, out = rollout_args(**arrays)
-        self._chk(self.L.kad_rollout_plan(self.h, ctypes.byref(b), ctypes.byref(v)))
-        return out
+        return self._consume("kad_rollout_plan", rollout_args(**arrays))
 
     def rollout_timing(self):
         """kad_rollout_timing: device ms of the last rollout_plan() — (rollout_kernel,)."""
-        ms = (ctypes.c_float * 1)()
-        self._chk(self.L.kad_rollout_timing(self.h, ms))
-        return (float(ms[0]),)
+        return self._timing("rollout", 1)
 
     def rollout_last_route(self) -> dict:
         """kad_rollout_last_route: what the last rollout_plan() launched (rollout_route_eval's record)."""
-        out = (ctypes.c_int32 * len(ROLLOUT_ROUTE))()
-        self._chk(self.L.kad_rollout_last_route(self.h, out))
-        return dict(zip(ROLLOUT_ROUTE, out))
+        return self._last_route("rollout", ROLLOUT_ROUTE)
 
     def rollout_debug_route(self, width: int = 0, long_min: int = 0, serial: int = 0) -> None:
         """kad_rollout_debug_route: the group width / long_min of the following rollout_plan() calls (0: the
         route's own); serial = 1 walks every object serially. Measurement only."""
-        self._chk(self.L.kad_rollout_debug_route(self.h, width, long_min, serial))
+        self._debug_route("rollout", width, long_min, serial)
 
     def dispatch_plan(self, fill: int = 0, **arrays) -> dict:
         """kad_dispatch_plan → {out_cluster, out_op, out_status (object o's entries at out_off[o] .. + count[o]),
         count[O], n_ops[O], n_selected[O], obj_result[O]}. Arguments as :func:`dispatch_args`
         (dispatch.DispatchBatch.arrays()); the slots behind an object's entries keep ``fill``."""
-        b, v, _keepalive, out = dispatch_args(fill, **arrays)
-        self._chk(self.L.kad_dispatch_plan(self.h, ctypes.byref(b), ctypes.byref(v)))
-        return out
+        return self._consume("kad_dispatch_plan", dispatch_args(fill, **arrays))
 
     def dispatch_timing(self):
         """kad_dispatch_timing: ms of the last dispatch_plan() — (inputs to the device, dispatch_wave_kernel,
         outputs back)."""
-        ms = (ctypes.c_float * 3)()
-        self._chk(self.L.kad_dispatch_timing(self.h, ms))
-        return tuple(float(x) for x in ms)
+        return self._timing("dispatch", 3)
 
     def dispatch_last_route(self) -> dict:
         """kad_dispatch_last_route: what the last dispatch_plan() launched (dispatch_route_eval's record)."""
-        out = (ctypes.c_int32 * len(DISPATCH_ROUTE))()
-        self._chk(self.L.kad_dispatch_last_route(self.h, out))
-        return dict(zip(DISPATCH_ROUTE, out))
+        return self._last_route("dispatch", DISPATCH_ROUTE)
 
     def select_rows(self, rows: Sequence[Sequence[int]], max_clusters: Sequence[Optional[int]], flags: int = 0):
         """MaxCluster on explicit score rows → per row (status, sorted selected positions)."""
@@ -1095,9 +1051,7 @@ class Context:
         self._chk(self.L.kad_trigger_run(self.h))
 
     def trigger_timing(self):
-        ms = (ctypes.c_float * 2)()
-        self._chk(self.L.kad_trigger_timing(self.h, ms))
-        return float(ms[0]), float(ms[1])
+        return self._timing("trigger", 2)
 
     def trigger_download(self) -> np.ndarray:
         out = np.zeros(max(1, self._trig_n), np.uint32)

@@ -4,8 +4,9 @@ tests/arena_main.cpp includes the layout half of csrc/kad_arena.h and first_bad 
 csrc/kad_ctx.h (KAD_HOST_ONLY: no HIP header, no device). It is compiled here with the host compiler under
 AddressSanitizer and UndefinedBehaviorSanitizer and run as its own process; nothing is loaded into Python.
 It checks that parts are 256-B aligned and disjoint, that empty parts keep a slot and absent ones give a null
-pointer, total() of the five consumer layouts at n = 0, 1 and 65 537 (past first_bad's parallel threshold),
-and that csr_bad agrees with one serial pass on a non-zero start, a decrease at the first, a middle, the last
+pointer, that every bound pointer lands at its part's offset, that a field of 1, 4 or 8 bytes reserves its
+count times its width, that only outputs bound to a host destination are fetched, total() of the consumer
+layouts at n = 0, 1 and 65 537 (past first_bad's parallel threshold), and that csr_bad agrees with one serial pass on a non-zero start, a decrease at the first, a middle, the last
 and the 65 536th offset, and an entry equal to lo - 1 and to hi."""
 import os
 import shutil
