@@ -1167,6 +1167,85 @@ int kad_dispatch_timing(kad_ctx* ctx, float ms[3]);
 int kad_dispatch_route_eval(int32_t n_clusters, int32_t n_objects, int32_t n_cu, int32_t* out);
 int kad_dispatch_last_route(kad_ctx* ctx, int32_t* out);
 
+/* ------------------------------------------------------ policy reference counts
+ * The policy reference counter (pkg/controllers/policyrc) keeps, per PropagationPolicy / ClusterPropagationPolicy and
+ * per OverridePolicy / ClusterOverridePolicy, the number of federated objects of one type that reference it
+ * (Counter.Update, counter.go:50-80: a map under one mutex, "only one worker is meaningful", :33-34) and writes it
+ * into the policy's status.typedRefCount and status.refCount (reconcilePersist, controller.go:280-366).
+ * kad_policyrc_count does the counting and the persist decision for a batch of reference changes.
+ *
+ * The device never sees objects: the caller interns policy keys to ids 0 .. n_policies - 1 (propagation and override
+ * policies share the table, so one call serves both of the reference's counters) and lists one id per reference
+ * removed in dec_ids[n_dec] (an object's previously known policies, counter.go:67-74) and one per reference added in
+ * inc_ids[n_inc] (:76-78); either list may be null when its count is 0. Per policy: count[P] = the counter's current
+ * value; stored_typed[P] = the policy's stored TypedRefCount.Count for this type config's (group, resource), 0
+ * without such an entry (controller.go:320-335); stored_rest[P] = the sum of its other typed entries;
+ * stored_total[P] = its status.refCount; pol_flags[P]: KAD_PRC_POL_EXISTS = the policy is in the store
+ * (controller.go:307-310), KAD_PRC_POL_ENQUEUED = it is to be persisted even if no id names it (a policy informer
+ * event: the informers' EnqueueObject, controller.go:146-192).
+ *
+ * Outputs: new_count[P] = count + adds - removals; new_total[P] = stored_rest + new_count (both wrap as Go's
+ * int64); state[P]: KAD_PRC_FLAGGED = at least one id of either list names the policy (the reference's
+ * flaggedPolicies as a set: a policy removed and added equally often is flagged with a delta of 0), KAD_PRC_UPDATE =
+ * EXISTS and (FLAGGED or ENQUEUED) and (new_count != stored_typed or new_total != stored_total): reconcilePersist's
+ * hasChange (controller.go:337-353), KAD_PRC_NEGATIVE = new_count < 0; n_negative[1] = the policies with
+ * KAD_PRC_NEGATIVE.
+ * Declared deviation: the reference panics the moment a decrement takes a count below 0 (counter.go:69-72). The call
+ * reports the final count instead and never aborts: a count that dips below 0 between two events of one batch and
+ * recovers is not seen. The caller's bookkeeping keeps the invariant (an id is only ever removed after it was added).
+ *
+ * Everything is validated on the host before anything is launched (KAD_EINVAL): a negative count, a null array with a
+ * non-zero count, an id outside [0, P), unknown pol_flags bits, reserved != 0, a missing output. Runs on the ctx
+ * stream (prc_count_kernel builds the two histograms, prc_apply_kernel the outputs: kad_policyrc.hip); blocks until
+ * the outputs are in the caller's buffers. Everything is integer: the results do not depend on the order in which
+ * ids arrive. Needs no snapshot and reads no resident state, so a kad_group member accepts it. Leaves the last
+ * results, the timings and any later kad_schedule as they were. n_policies == 0 returns 0 without launching. */
+#define KAD_PRC_POL_EXISTS 1u
+#define KAD_PRC_POL_ENQUEUED 2u
+#define KAD_PRC_FLAGGED 1u
+#define KAD_PRC_UPDATE 2u
+#define KAD_PRC_NEGATIVE 4u
+typedef struct kad_policyrc_batch {
+  int32_t n_policies; /* P */
+  int32_t n_dec;
+  int32_t n_inc;
+  int32_t reserved;   /* 0 */
+  const int32_t* dec_ids;      /* [n_dec] in [0, P) */
+  const int32_t* inc_ids;      /* [n_inc] in [0, P) */
+  const int64_t* count;        /* [P] */
+  const int64_t* stored_typed; /* [P] */
+  const int64_t* stored_rest;  /* [P] */
+  const int64_t* stored_total; /* [P] */
+  const uint8_t* pol_flags;    /* [P] KAD_PRC_POL_* */
+} kad_policyrc_batch;
+typedef struct kad_policyrc_view {
+  int64_t* new_count;  /* [P] */
+  int64_t* new_total;  /* [P] */
+  uint8_t* state;      /* [P] KAD_PRC_FLAGGED | _UPDATE | _NEGATIVE */
+  int32_t* n_negative; /* [1] */
+} kad_policyrc_view;
+int kad_policyrc_count(kad_ctx* ctx, const kad_policyrc_batch* batch, const kad_policyrc_view* out);
+/* Host only (no device, no ctx): the same validation. */
+int kad_policyrc_check(const kad_policyrc_batch* batch, const kad_policyrc_view* out);
+/* Times of the last kad_policyrc_count that launched, from HIP events: ms[0] = the inputs' copies to the device,
+ * ms[1] = the zeroing of the histograms and prc_count_kernel, ms[2] = prc_apply_kernel. */
+int kad_policyrc_timing(kad_ctx* ctx, float ms[3]);
+/* What a kad_policyrc_count launches, as the library's one decision computes it (csrc/kad_policyrc.h
+ * route_policyrc; no device work, no ctx): n_ids = n_dec + n_inc. out[KAD_PRC_ROUTE_FIELDS] is [0] the count
+ * kernel's path: 0 = LDS-private (every block counts into 2 * P bins of its own in LDS and adds its non-zero bins
+ * to the histograms), 1 = global (every wave merges runs of equal neighbouring ids and adds one global atomic per
+ * run), [1] the bins limit: the largest P of the LDS-private path, [2] block threads, [3] count-kernel blocks (0
+ * without ids: only the zeroing and the apply kernel run), [4] ids a lane reads per step, [5] apply-kernel blocks
+ * (one thread per policy). kad_policyrc_last_route: the same record for the last kad_policyrc_count that launched
+ * (KAD_ESTATE before one). */
+#define KAD_PRC_ROUTE_FIELDS 6
+int kad_policyrc_route_eval(int32_t n_policies, int64_t n_ids, int32_t n_cu, int32_t* out);
+int kad_policyrc_last_route(kad_ctx* ctx, int32_t* out);
+/* Measurement and tests only: the count kernel's path of the following kad_policyrc_count calls: 0 = the route's
+ * own, 1 = LDS-private, 2 = global. LDS-private forced on more policies than the bins limit: KAD_EINVAL from that
+ * call. */
+int kad_policyrc_debug_route(kad_ctx* ctx, int32_t force_path);
+
 /* ------------------------------------------------ result application (§8 f3)
  * applySchedulingResult (pkg/controllers/scheduler/scheduler.go:632-695) writes a unit's result into its
  * federated object: the scheduler controller's placement (util.SetPlacementClusterNames,

@@ -69,6 +69,7 @@ class BatchReconciler:
         self.scheduler = BatchScheduler(self.ctx)
         self._clusters_key = None
         self._pass = None  # the batch the last reconcile left resident (last_pass)
+        self.policy_refs = None  # policyrc.PolicyRefCounter, from the first reconcile_policy_refcounts on
 
     def _framework(self, profile: Optional[dict]) -> F.Framework:
         """createFramework (scheduler.go:492, profile.go:52-82): default plugins + the profile's changes."""
@@ -550,6 +551,28 @@ class BatchReconciler:
         if not len(batch):
             return []
         return batch.apply(self.ctx.dispatch_plan(**batch.arrays()))
+
+    # ------------------------------------------------------------------ policy reference counts
+    def reconcile_policy_refcounts(self, events: Sequence[Tuple[object, Optional[dict]]], policies: Dict[tuple, dict],
+                                   enqueued: Sequence[tuple] = ()) -> Tuple[list, list]:
+        """The policy reference counter for a batch of federated-object events (pkg/controllers/policyrc:
+        reconcileCount, controller.go:231-278, Counter.Update, counter.go:50-80, reconcilePersist,
+        controller.go:280-366): ``events[i]`` is (the object's qualified name, the federated object as the informer
+        holds it now, or None once it is deleted), in order; ``policies`` the propagation and override policy
+        objects in the store by policyrc key ``(kind, namespace, name)``; ``enqueued`` the keys a policy informer
+        event asks to persist. The counts live on this reconciler between calls (policyrc.PolicyRefCounter). One
+        kad_policyrc_count answers every policy; the policies whose numbers moved get ``status.typedRefCount`` and
+        ``status.refCount`` written in place. Returns (the flagged policy keys, the (key, policy) pairs to
+        ``UpdateStatus``); raises policyrc.PolicyRefCountError where the reference panics. The informers and the
+        ``UpdateStatus`` call with its conflict retry stay with the caller."""
+        from . import policyrc as PR
+
+        if self.policy_refs is None:
+            self.policy_refs = PR.PolicyRefCounter(self.type_config)
+        self.policy_refs.observe(events)
+        arrays = self.policy_refs.arrays(policies, enqueued)
+        result = self.ctx.policyrc_count(**arrays) if len(arrays["pol_flags"]) else None
+        return self.policy_refs.apply(result, policies)
 
     # ------------------------------------------------------------------ the reconcile over JSON texts
     def reconcile_texts(self, texts: Sequence, policies: Sequence, clusters: List[T.FederatedCluster],

@@ -146,6 +146,18 @@ class DispatchView(ctypes.Structure):  # kad_dispatch_view
                 ("obj_result", ctypes.c_void_p)]
 
 
+class PolicyrcBatch(ctypes.Structure):  # kad_policyrc_batch
+    _fields_ = [("n_policies", ctypes.c_int32), ("n_dec", ctypes.c_int32), ("n_inc", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("dec_ids", ctypes.c_void_p), ("inc_ids", ctypes.c_void_p),
+                ("count", ctypes.c_void_p), ("stored_typed", ctypes.c_void_p), ("stored_rest", ctypes.c_void_p),
+                ("stored_total", ctypes.c_void_p), ("pol_flags", ctypes.c_void_p)]
+
+
+class PolicyrcView(ctypes.Structure):  # kad_policyrc_view
+    _fields_ = [("new_count", ctypes.c_void_p), ("new_total", ctypes.c_void_p), ("state", ctypes.c_void_p),
+                ("n_negative", ctypes.c_void_p)]
+
+
 _lib = None
 
 
@@ -206,6 +218,7 @@ _CONSUMER_ABI = {
     "sagg": ("kad_status_aggregate", (), (_I32, _I32, _I64, _I32), (_I32, _I32)),
     "rollout": ("kad_rollout_plan", (ctypes.c_void_p,), (_I32, _I32, _I64, _I32, _I32), (_I32, _I32, _I32)),
     "dispatch": ("kad_dispatch_plan", (), (_I32, _I32, _I32), None),
+    "policyrc": ("kad_policyrc_count", (), (_I32, _I64, _I32), (_I32,)),
 }
 
 
@@ -605,6 +618,41 @@ def dispatch_check(**arrays) -> int:
     return _check("dispatch", dispatch_args(**arrays))
 
 
+POLICYRC_ROUTE = ("path", "bins", "threads", "grid", "vec", "apply_grid")
+POLICYRC_PATHS = ("LDS", "GLOBAL")  # the record's path; policyrc_debug_route forces 1 + its index
+PRC_POL_EXISTS, PRC_POL_ENQUEUED = 1, 2
+PRC_FLAGGED, PRC_UPDATE, PRC_NEGATIVE = 1, 2, 4
+
+
+def policyrc_route_eval(n_policies: int, n_ids: int, n_cu: int = 256) -> dict:
+    """kad_policyrc_route_eval: the launch decision of a policyrc_count over n_ids = n_dec + n_inc ids (needs no
+    GPU)."""
+    return _route_eval("policyrc", POLICYRC_ROUTE, n_policies, n_ids, n_cu, error=KadError)
+
+
+_POLICYRC_IN = (("dec_ids", np.int32), ("inc_ids", np.int32), ("count", np.int64), ("stored_typed", np.int64),
+                ("stored_rest", np.int64), ("stored_total", np.int64), ("pol_flags", np.uint8))
+_POLICYRC_OUT = (("new_count", np.int64, 0), ("new_total", np.int64, 0), ("state", np.uint8, 0), ("n_negative", np.int32, 1))
+
+
+def policyrc_args(**arrays):
+    """The kad_policyrc_batch / kad_policyrc_view of one call with the arrays that back them (the batch's fields by
+    name; the counts are taken from pol_flags, dec_ids and inc_ids as they are, so that a malformed batch reaches
+    the library's validation; ``n_policies``, ``n_dec``, ``n_inc`` and ``reserved`` override them). Returns (batch,
+    view, the input arrays, the output arrays by name)."""
+    a = _flat(_POLICYRC_IN, arrays)
+    counts = tuple(int(arrays.get(k, len(a[src]) if src in a else 0))
+                   for k, src in (("n_policies", "pol_flags"), ("n_dec", "dec_ids"), ("n_inc", "inc_ids")))
+    P = max(0, counts[0], len(a["pol_flags"]) if "pol_flags" in a else 0)
+    return _call_args(PolicyrcBatch, PolicyrcView, counts + (int(arrays.get("reserved", 0)),), _POLICYRC_IN,
+                      _POLICYRC_OUT, a, {0: P, 1: 1})
+
+
+def policyrc_check(**arrays) -> int:
+    """kad_policyrc_check: kad_policyrc_count's validation of :func:`policyrc_args` arguments; no GPU."""
+    return _check("policyrc", policyrc_args(**arrays))
+
+
 class Context:
     """A kad_ctx: one HIP device, one stream, resident snapshot + batch."""
 
@@ -984,6 +1032,25 @@ class Context:
     def dispatch_last_route(self) -> dict:
         """kad_dispatch_last_route: what the last dispatch_plan() launched (dispatch_route_eval's record)."""
         return self._last_route("dispatch", DISPATCH_ROUTE)
+
+    def policyrc_count(self, **arrays) -> dict:
+        """kad_policyrc_count → {new_count[P], new_total[P], state[P] (PRC_FLAGGED | PRC_UPDATE | PRC_NEGATIVE),
+        n_negative[1]}. Arguments as :func:`policyrc_args` (policyrc.PolicyRefCounter.arrays())."""
+        return self._consume("kad_policyrc_count", policyrc_args(**arrays))
+
+    def policyrc_timing(self):
+        """kad_policyrc_timing: ms of the last policyrc_count() — (inputs to the device, the zeroing and
+        prc_count_kernel, prc_apply_kernel)."""
+        return self._timing("policyrc", 3)
+
+    def policyrc_last_route(self) -> dict:
+        """kad_policyrc_last_route: what the last policyrc_count() launched (policyrc_route_eval's record)."""
+        return self._last_route("policyrc", POLICYRC_ROUTE)
+
+    def policyrc_debug_route(self, path: int = 0) -> None:
+        """kad_policyrc_debug_route: the count kernel's path of the following policyrc_count() calls (0: the
+        route's own, 1: LDS-private, 2: global)."""
+        self._debug_route("policyrc", path)
 
     def select_rows(self, rows: Sequence[Sequence[int]], max_clusters: Sequence[Optional[int]], flags: int = 0):
         """MaxCluster on explicit score rows → per row (status, sorted selected positions)."""
