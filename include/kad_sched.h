@@ -1246,6 +1246,190 @@ int kad_policyrc_last_route(kad_ctx* ctx, int32_t* out);
  * call. */
 int kad_policyrc_debug_route(kad_ctx* ctx, int32_t force_path);
 
+/* ------------------------------------------------------ sync completion: propagated versions and status
+ * The second half of the sync controller's syncToClusters (pkg/controllers/sync/controller.go:425-596), after
+ * kad_dispatch_plan has decided the operations: kad_sync_needs_update is the version check of every update
+ * (dispatch/managed.go:450-460, util/propagatedversion.go:54-119, sync/version/manager.go:119-148) and runs before
+ * the operations; kad_sync_finish closes the reconcile after dispatcher.Wait() (controller.go:546-596): Wait's
+ * status transitions (managed.go:137-155), the new cluster versions and whether the PropagatedVersion object is
+ * written (manager.go:152-210, 448-479), ConvertVersionMapToGenerationMap (propagatedversion.go:138-157) and
+ * status.update (sync/status/status.go:87-229).
+ *
+ * Shared conventions. Cluster ids 0 .. C - 1 index the joined clusters in ascending byte order of their names, so
+ * that ascending id is sort.Strings / SortClusterVersions order; C <= KAD_DISPATCH_MAX_CLUSTERS, more is
+ * KAD_EUNSUPPORTED. The device never sees a version string: the caller interns the distinct version strings of the
+ * batch into a table of V entries, id 0 = no version (its flags are 0), equal id <=> equal string;
+ * ver_flags[V]: KAD_SYNC_VER_HAS_GEN = ConvertVersionMapToGenerationMap has an entry for the string, ver_gen[V] its
+ * value (0 for an "rv:" prefix, the parsed number for a "gen:" prefix that strconv.ParseInt(.., 10, 64) accepts);
+ * KAD_SYNC_VER_IS_GEN = the string starts with "gen:" (propagatedversion.go:118). Propagation statuses are the u8
+ * codes KAD_SYNC_ST_*: 1 .. 23 in the order of the constants of pkg/apis/types/v1alpha1/types_status.go:71-99,
+ * 0 = none. Aggregate reasons are interned per batch into R ids, 0 = AggregateSuccess; the ids of CheckClusters and
+ * NamespaceNotFederated are given in the batch (distinct, in [1, R)).
+ *
+ * kad_sync_needs_update: one row per (object, cluster) whose operation is an update. row_obj / row_cluster /
+ * row_target[n_rows]: the object, the cluster and the id of ObjectVersion(clusterObj); row_flags: KAD_SYNC_ROW_* =
+ * what ObjectNeedsUpdate reads from the two objects, decided on the host (replicas equal; maxSurge equal;
+ * maxUnavailable equal; ObjectMetaObjEquivalent). obj_flags[O]: KAD_SYNC_VERSIONS_CURRENT = a PropagatedVersion is
+ * stored and its template and override versions equal the object's (manager.go:140-141); rec_off[O + 1] /
+ * rec_cluster / rec_version: its recorded cluster versions, strictly ascending by cluster within an object.
+ * recorded[row] = the version VersionForCluster returns: the object's entry for the cluster (binary search), 0
+ * without one or when the object is not VERSIONS_CURRENT. needs_update[row] = recorded != target, or one of the three
+ * equality flags is clear, or the target is IS_GEN and META_EQUIVALENT is clear. One lane per row.
+ *
+ * kad_sync_finish: per object four lists as CSRs, each strictly ascending by cluster id: sel (the selected clusters),
+ * ent (the dispatcher's records: cluster, the status recorded when the operation ended and before Wait's
+ * transitions, the version recordVersion recorded or 0), oldv (the stored PropagatedVersion's cluster versions) and
+ * olds (the stored status.clusters: cluster, status, generation). obj_flags[O] (KAD_SYNC_OBJ_*): VERSION_EXISTS,
+ * VERSIONS_CURRENT (needs VERSION_EXISTS), OLDV_NIL (the stored list is absent, not empty: reflect.DeepEqual tells
+ * them apart; oldv must be empty), OLDV_IRREGULAR (the caller dropped an unknown cluster or a duplicate, keeping the
+ * first as updateClusterVersions does, or reordered), RESOURCES_UPDATED, SCALARS_CHANGED (syncedGeneration or
+ * collisionCount moved, status.go:94-102), COND_EXISTS, COND_TRUE, STATUS_ON_HOST. Without VERSION_EXISTS oldv is
+ * empty. reason_in[O]: the reason setFederatedStatus hands to update (NamespaceNotFederated applied by the caller,
+ * controller.go:649-656); cond_reason[O]: the stored condition's reason id, -1 for a stored condition that can equal
+ * no new one (a status that is neither True nor False). ver_off[O + 1] / st_off[O + 1]: where an object's version
+ * and status entries go; capacities of at least |ent| + |oldv| and |ent|.
+ * Per object: (1) CreationTimedOut / UpdateTimedOut become OK, DeletionTimedOut WaitingForRemoval, a
+ * LabelRemovalTimedOut entry loses its status. (2) The new cluster versions: every ent with a version, and, only if
+ * VERSIONS_CURRENT, every oldv entry whose cluster is selected and has no ent version; ascending from ver_off[o],
+ * ver_count[o] of them. (3) ver_write[o] = !VERSION_EXISTS, !VERSIONS_CURRENT, OLDV_IRREGULAR, OLDV_NIL with an empty
+ * new list, or the new list differs from oldv (PropagatedVersionStatusEquivalent). (4) The status map is the ent
+ * with a status left, the generation map the ent with a HAS_GEN version; clustersDiffers compares len(olds) with
+ * both sizes separately (status.go:164-169), then every olds entry with the maps. (5) reason_out = reason_in, or
+ * CheckClusters where that is success and a status is not OK. (6) status.clusters: one (cluster, status, generation
+ * or 0) per status-map entry from st_off[o], st_count[o] of them, always written. (7) obj_out[o] (KAD_SYNC_OUT_*):
+ * CLUSTERS_CHANGED; CHANGES_PROPAGATED = that, or a non-empty status map with RESOURCES_UPDATED; TRANSITION =
+ * !COND_EXISTS or COND_TRUE != (reason == success) or cond_reason != reason; UPDATE_REQUIRED = CHANGES_PROPAGATED or
+ * TRANSITION; STATUS_WRITE = SCALARS_CHANGED or UPDATE_REQUIRED. Slots behind an object's counts are unspecified.
+ * Declared deviations: an ent version of 0 is "no record": the reference could hold an empty string there, which
+ * nothing in it records. Objects whose Wait() timed out never reach this code (controller.go:550-554): the caller
+ * leaves them out. A stored status.clusters with a duplicate name, a cluster that is not joined or a status outside
+ * the constants meets corners of Go's map lookups ([a, a] against {a, b} does not differ): the caller marks the
+ * object STATUS_ON_HOST (olds must then be empty), the device writes 0 to its st_count, obj_out and reason_out and
+ * the caller decides it; its version outputs still come from the device.
+ *
+ * Everything is validated on the host before anything is launched (KAD_EINVAL): counts, offsets, lists not strictly
+ * ascending, ids outside [0, C), version ids outside [0, V), unknown status codes or flag bits, reason ids,
+ * capacities below the bound, missing arrays. Both run on the ctx stream (syncfin_rows_kernel; syncfin_kernel:
+ * kad_syncfin.hip) and block until the outputs are in the caller's buffers. Integers only, no atomics: the results
+ * do not depend on any order. They need no snapshot and read no resident state, so a kad_group member accepts them;
+ * they leave the last results, the timings and any later kad_schedule as they were. n_objects == 0 (n_rows == 0)
+ * returns 0 without launching. */
+#define KAD_SYNC_ST_OK 1u
+#define KAD_SYNC_ST_WAITING_FOR_REMOVAL 2u
+#define KAD_SYNC_ST_CREATION_TIMED_OUT 20u
+#define KAD_SYNC_ST_UPDATE_TIMED_OUT 21u
+#define KAD_SYNC_ST_DELETION_TIMED_OUT 22u
+#define KAD_SYNC_ST_LABEL_REMOVAL_TIMED_OUT 23u
+#define KAD_SYNC_ST_MAX 23u
+#define KAD_SYNC_VER_HAS_GEN 1u
+#define KAD_SYNC_VER_IS_GEN 2u
+#define KAD_SYNC_ROW_REPLICAS_EQUAL 1u
+#define KAD_SYNC_ROW_SURGE_EQUAL 2u
+#define KAD_SYNC_ROW_UNAVAILABLE_EQUAL 4u
+#define KAD_SYNC_ROW_META_EQUIVALENT 8u
+#define KAD_SYNC_VERSIONS_CURRENT 1u /* kad_sync_needs_update's obj_flags */
+#define KAD_SYNC_OBJ_VERSION_EXISTS 1u
+#define KAD_SYNC_OBJ_VERSIONS_CURRENT 2u
+#define KAD_SYNC_OBJ_OLDV_NIL 4u
+#define KAD_SYNC_OBJ_OLDV_IRREGULAR 8u
+#define KAD_SYNC_OBJ_RESOURCES_UPDATED 16u
+#define KAD_SYNC_OBJ_SCALARS_CHANGED 32u
+#define KAD_SYNC_OBJ_COND_EXISTS 64u
+#define KAD_SYNC_OBJ_COND_TRUE 128u
+#define KAD_SYNC_OBJ_STATUS_ON_HOST 256u
+#define KAD_SYNC_OUT_CLUSTERS_CHANGED 1u
+#define KAD_SYNC_OUT_CHANGES_PROPAGATED 2u
+#define KAD_SYNC_OUT_TRANSITION 4u
+#define KAD_SYNC_OUT_UPDATE_REQUIRED 8u
+#define KAD_SYNC_OUT_STATUS_WRITE 16u
+typedef struct kad_sync_nu_batch {
+  int32_t n_clusters; /* C */
+  int32_t n_objects;  /* O */
+  int32_t n_rows;
+  int32_t n_versions; /* V >= 1 */
+  const int32_t* row_obj;     /* [n_rows] in [0, O) */
+  const int32_t* row_cluster; /* [n_rows] in [0, C) */
+  const int32_t* row_target;  /* [n_rows] in [0, V) */
+  const uint8_t* row_flags;   /* [n_rows] KAD_SYNC_ROW_* */
+  const uint8_t* obj_flags;   /* [O] KAD_SYNC_VERSIONS_CURRENT */
+  const int32_t* rec_off;     /* [O + 1] */
+  const int32_t* rec_cluster; /* [rec_off[O]] */
+  const int32_t* rec_version; /* [rec_off[O]] in [0, V) */
+  const uint8_t* ver_flags;   /* [V] KAD_SYNC_VER_* */
+} kad_sync_nu_batch;
+typedef struct kad_sync_nu_view {
+  uint8_t* needs_update; /* [n_rows] */
+  int32_t* recorded;     /* [n_rows] */
+} kad_sync_nu_view;
+int kad_sync_needs_update(kad_ctx* ctx, const kad_sync_nu_batch* batch, const kad_sync_nu_view* out);
+/* Host only (no device, no ctx): the same validation. */
+int kad_sync_needs_update_check(const kad_sync_nu_batch* batch, const kad_sync_nu_view* out);
+/* ms[0] = the inputs' copies to the device, ms[1] = syncfin_rows_kernel, ms[2] = the outputs' copies back. */
+int kad_sync_needs_update_timing(kad_ctx* ctx, float ms[3]);
+/* csrc/kad_syncfin.h route_sync_rows: out[KAD_SYNC_NU_ROUTE_FIELDS] is [0] block threads, [1] blocks (a lane per
+ * row; at most 8 blocks a CU), [2] rows between two consecutive rows of one lane. */
+#define KAD_SYNC_NU_ROUTE_FIELDS 3
+int kad_sync_needs_update_route_eval(int32_t n_rows, int32_t n_cu, int32_t* out);
+int kad_sync_needs_update_last_route(kad_ctx* ctx, int32_t* out);
+
+typedef struct kad_sync_fin_batch {
+  int32_t n_clusters; /* C */
+  int32_t n_objects;  /* O */
+  int32_t n_versions; /* V >= 1 */
+  int32_t n_reasons;  /* R >= 3 */
+  int32_t reason_check_clusters;
+  int32_t reason_ns_not_federated;
+  const uint16_t* obj_flags;   /* [O] KAD_SYNC_OBJ_* */
+  const int32_t* reason_in;    /* [O] in [0, R) */
+  const int32_t* cond_reason;  /* [O] in [-1, R) */
+  const int32_t* sel_off;      /* [O + 1] */
+  const int32_t* sel_cluster;
+  const int32_t* ent_off;      /* [O + 1] */
+  const int32_t* ent_cluster;
+  const uint8_t* ent_status;   /* 0 .. KAD_SYNC_ST_MAX */
+  const int32_t* ent_version;  /* in [0, V) */
+  const int32_t* oldv_off;     /* [O + 1] */
+  const int32_t* oldv_cluster;
+  const int32_t* oldv_version; /* in [1, V) */
+  const int32_t* olds_off;     /* [O + 1] */
+  const int32_t* olds_cluster;
+  const uint8_t* olds_status;  /* 1 .. KAD_SYNC_ST_MAX */
+  const int64_t* olds_gen;
+  const int64_t* ver_gen;      /* [V] */
+  const uint8_t* ver_flags;    /* [V] KAD_SYNC_VER_* */
+  const int64_t* ver_off;      /* [O + 1] */
+  const int64_t* st_off;       /* [O + 1] */
+} kad_sync_fin_batch;
+typedef struct kad_sync_fin_view {
+  int32_t* out_ver_cluster; /* [ver_off[O]] */
+  int32_t* out_ver_id;      /* [ver_off[O]] */
+  int32_t* ver_count;       /* [O] */
+  uint8_t* ver_write;       /* [O] */
+  int32_t* out_st_cluster;  /* [st_off[O]] */
+  uint8_t* out_st_status;   /* [st_off[O]] */
+  int64_t* out_st_gen;      /* [st_off[O]] */
+  int32_t* st_count;        /* [O] */
+  uint8_t* obj_out;         /* [O] KAD_SYNC_OUT_* */
+  int32_t* reason_out;      /* [O] */
+} kad_sync_fin_view;
+int kad_sync_finish(kad_ctx* ctx, const kad_sync_fin_batch* batch, const kad_sync_fin_view* out);
+/* Host only (no device, no ctx): the same validation. */
+int kad_sync_finish_check(const kad_sync_fin_batch* batch, const kad_sync_fin_view* out);
+/* ms[0] = the inputs' copies to the device, ms[1] = syncfin_kernel, ms[2] = the outputs' copies back. */
+int kad_sync_finish_timing(kad_ctx* ctx, float ms[3]);
+/* csrc/kad_syncfin.h route_sync_finish: an object's size is its longest list of ent, oldv and olds; n_long = the
+ * objects larger than the route's long_min, short_items = the summed sizes of the others.
+ * out[KAD_SYNC_FIN_ROUTE_FIELDS] is [0] lanes per object on the group path (the mean size of a short object over
+ * the elements a lane takes, a power of two in [1, 64]), [1] long_min, [2] block threads, [3] blocks of the group
+ * path, [4] blocks of the long path (one object per block), [5] objects between two consecutive objects of one lane
+ * group. */
+#define KAD_SYNC_FIN_ROUTE_FIELDS 6
+int kad_sync_finish_route_eval(int32_t n_objects, int32_t n_long, int64_t short_items, int32_t n_cu, int32_t* out);
+int kad_sync_finish_last_route(kad_ctx* ctx, int32_t* out);
+/* Measurement and tests only: the lane-group width (0 or a power of two in [1, 64]) and long_min (0: the route's
+ * own) of the following kad_sync_finish calls. */
+int kad_sync_finish_debug_route(kad_ctx* ctx, int32_t force_width, int32_t force_long_min);
+
 /* ------------------------------------------------ result application (§8 f3)
  * applySchedulingResult (pkg/controllers/scheduler/scheduler.go:632-695) writes a unit's result into its
  * federated object: the scheduler controller's placement (util.SetPlacementClusterNames,

@@ -537,9 +537,9 @@ class BatchReconciler:
         ``<plural>.<group>``). One kad_dispatch_plan answers every object (dispatch.DispatchBatch); returns per
         object a dispatch.DispatchOutcome: the computed placement, the operation started and the propagation status
         recorded per cluster, whether to recheck after dispatch, ComputePlacementFailed. Its ``selected`` and
-        ``rollout_members`` are what :meth:`reconcile_rollout` accepts. Objects being deleted (ensureDeletion), the
-        operations themselves, ObjectNeedsUpdate, Wait()'s status transitions and SetFederatedStatus stay with the
-        caller."""
+        ``rollout_members`` are what :meth:`reconcile_rollout` accepts. :meth:`reconcile_sync_versions` (before the
+        operations) and :meth:`reconcile_sync_finish` (after them) are the rest of syncToClusters; objects being
+        deleted (ensureDeletion) and the operations themselves are the caller's."""
         from . import dispatch as DI
 
         if finalizer is None:
@@ -551,6 +551,76 @@ class BatchReconciler:
         if not len(batch):
             return []
         return batch.apply(self.ctx.dispatch_plan(**batch.arrays()))
+
+    # ------------------------------------------------------------------ sync completion
+    def reconcile_sync_versions(self, objs: Sequence[dict], outcomes: Sequence, desired: Sequence[Dict[str, dict]],
+                                clusters: Sequence[str], versions, template_versions: Sequence[str],
+                                override_versions: Sequence[str]) -> List[Dict[str, Tuple[bool, str]]]:
+        """The version check of every update a :meth:`reconcile_dispatch` result starts (dispatch/managed.go:450-460:
+        VersionForCluster, then util.ObjectNeedsUpdate, util/propagatedversion.go:54-119), between the dispatch
+        plan and the operations: ``outcomes[i]`` is ``objs[i]``'s dispatch.DispatchOutcome, ``desired[i]`` per
+        cluster the object the update would write (overrides applied, fields retained), ``clusters`` the joined
+        cluster names, ``versions`` the syncfin.PropagatedVersions store and ``template_versions[i]`` /
+        ``override_versions[i]`` the object's two hashes. One kad_sync_needs_update answers every (object, cluster)
+        whose operation is an update; returns per object cluster → (the member object needs the update, the
+        recorded version): where it needs none the caller records that version (managed.go:455-460)."""
+        from . import dispatch as DI
+        from . import syncfin as SF
+
+        batch = SF.SyncFinishBatch(clusters)
+        for fed, oc, want, tv, ov in zip(objs, outcomes, desired, template_versions, override_versions):
+            md = fed.get("metadata") or {}
+            k = batch.add_versions(versions.status(md.get("namespace", ""), md.get("name", "")), tv, ov)
+            for name, op in sorted(oc.ops.items()):
+                if op == DI.OP_UPDATE:
+                    batch.add_update(k, name, want[name], oc.rollout_members[name], self.type_config.replicas_spec)
+        if not batch.rows:
+            return [{} for _ in objs]
+        a = batch.needs_update_arrays()
+        return batch.apply_needs_update(self.ctx.sync_needs_update(a.pop("n_clusters"), **a))
+
+    def reconcile_sync_finish(self, objs: Sequence[dict], outcomes: Sequence, op_results: Sequence[Dict[str, dict]],
+                              clusters: Sequence[str], versions, template_versions: Sequence[str],
+                              override_versions: Sequence[str], collision_counts: Optional[Sequence[Optional[int]]] = None,
+                              namespace_not_federated: Optional[Sequence[bool]] = None, now: Optional[str] = None) -> list:
+        """The close of syncToClusters for a batch of federated objects whose Wait() did not time out
+        (sync/controller.go:546-596): ``outcomes[i]`` is ``objs[i]``'s dispatch.DispatchOutcome and
+        ``op_results[i]`` per cluster what its operation left: ``{"status": the propagation status it recorded on
+        failure (absent: it succeeded, the timed-out status of the plan stands), "version": the version
+        recordVersion recorded (absent: none), "updated": the member object was written}``. One kad_sync_finish
+        decides Wait's transitions, the new cluster versions, status.clusters, the propagation condition and both
+        writes (syncfin.SyncFinishBatch). The PropagatedVersion status is put into ``versions`` where it is to be
+        written and ``objs[i]["status"]`` is replaced where UpdateStatus is due; ``now`` (RFC 3339, default the
+        clock) stamps the condition. Returns per object a syncfin.FinishOutcome. The API writes stay with the
+        caller."""
+        import time
+
+        from . import syncfin as SF
+
+        now = time.strftime("%Y-%m-%dT%H:%M:%SZ", time.gmtime()) if now is None else now
+        batch = SF.SyncFinishBatch(clusters)
+        for i, (fed, oc, ops, tv, ov) in enumerate(zip(objs, outcomes, op_results, template_versions, override_versions)):
+            md = fed.get("metadata") or {}
+            records = {n: (ops.get(n, {}).get("status") or s, ops.get(n, {}).get("version") or "") for n, s in oc.status.items()}
+            for n, r in ops.items():  # an operation on a cluster the plan gave no status
+                records.setdefault(n, (r.get("status") or "", r.get("version") or ""))
+            gen = md.get("generation", 0)
+            batch.add(fed.get("status"), gen if isinstance(gen, int) else 0, collision_counts[i] if collision_counts else None,
+                      oc.selected, records, any(r.get("updated") for r in ops.values()),
+                      versions.status(md.get("namespace", ""), md.get("name", "")), tv, ov, oc.reason or SF.AGGREGATE_SUCCESS,
+                      bool(namespace_not_federated[i]) if namespace_not_federated else False)
+        if not len(batch):
+            return []
+        a = batch.finish_arrays()
+        head = [a.pop(k) for k in ("n_clusters", "n_reasons", "reason_check_clusters", "reason_ns_not_federated")]
+        out = batch.apply(self.ctx.sync_finish(*head, **a), now)
+        for fed, o in zip(objs, out):
+            md = fed.get("metadata") or {}
+            if o.version_write:
+                versions.set_status(md.get("namespace", ""), md.get("name", ""), o.version_status)
+            if o.status_write:
+                fed["status"] = o.status
+        return out
 
     # ------------------------------------------------------------------ policy reference counts
     def reconcile_policy_refcounts(self, events: Sequence[Tuple[object, Optional[dict]]], policies: Dict[tuple, dict],

@@ -105,7 +105,7 @@ struct Stage {
   kad::GroupForce force;
 };
 enum StageId { STG_DIFF, STG_EXPLAIN, STG_OVERRIDE, STG_FOLLOWER, STG_MIGRATE, STG_TRIGGER, STG_CSTAT, STG_SAGG,
-               STG_ROLLOUT, STG_DISPATCH, STG_POLICYRC, STG_COUNT };
+               STG_ROLLOUT, STG_DISPATCH, STG_POLICYRC, STG_SYNCNU, STG_SYNCFIN, STG_COUNT };
 
 struct kad_ctx {
   int device = 0;

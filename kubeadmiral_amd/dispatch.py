@@ -14,8 +14,9 @@ module restates everything around that loop:
   kad_dispatch_plan's arrays, and its outputs turned back into names (``apply``);
 * ``plan_numpy`` — the loop itself, vectorised over sorted (object, cluster) keys, over the same arrays.
 
-Deleting objects (ensureDeletion), the operations themselves, ObjectNeedsUpdate, Wait()'s status transitions and
-SetFederatedStatus stay with the caller.
+ObjectNeedsUpdate, Wait()'s status transitions, the propagated versions and SetFederatedStatus are syncfin.py's
+(kad_sync_needs_update, kad_sync_finish). Deleting objects (ensureDeletion) and the operations themselves are the
+caller's.
 """
 
 from __future__ import annotations

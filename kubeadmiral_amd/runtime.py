@@ -158,6 +158,37 @@ class PolicyrcView(ctypes.Structure):  # kad_policyrc_view
                 ("n_negative", ctypes.c_void_p)]
 
 
+class SyncNuBatch(ctypes.Structure):  # kad_sync_nu_batch
+    _fields_ = [("n_clusters", ctypes.c_int32), ("n_objects", ctypes.c_int32), ("n_rows", ctypes.c_int32),
+                ("n_versions", ctypes.c_int32), ("row_obj", ctypes.c_void_p), ("row_cluster", ctypes.c_void_p),
+                ("row_target", ctypes.c_void_p), ("row_flags", ctypes.c_void_p), ("obj_flags", ctypes.c_void_p),
+                ("rec_off", ctypes.c_void_p), ("rec_cluster", ctypes.c_void_p), ("rec_version", ctypes.c_void_p),
+                ("ver_flags", ctypes.c_void_p)]
+
+
+class SyncNuView(ctypes.Structure):  # kad_sync_nu_view
+    _fields_ = [("needs_update", ctypes.c_void_p), ("recorded", ctypes.c_void_p)]
+
+
+class SyncFinBatch(ctypes.Structure):  # kad_sync_fin_batch
+    _fields_ = [("n_clusters", ctypes.c_int32), ("n_objects", ctypes.c_int32), ("n_versions", ctypes.c_int32),
+                ("n_reasons", ctypes.c_int32), ("reason_check_clusters", ctypes.c_int32),
+                ("reason_ns_not_federated", ctypes.c_int32), ("obj_flags", ctypes.c_void_p), ("reason_in", ctypes.c_void_p),
+                ("cond_reason", ctypes.c_void_p), ("sel_off", ctypes.c_void_p), ("sel_cluster", ctypes.c_void_p),
+                ("ent_off", ctypes.c_void_p), ("ent_cluster", ctypes.c_void_p), ("ent_status", ctypes.c_void_p),
+                ("ent_version", ctypes.c_void_p), ("oldv_off", ctypes.c_void_p), ("oldv_cluster", ctypes.c_void_p),
+                ("oldv_version", ctypes.c_void_p), ("olds_off", ctypes.c_void_p), ("olds_cluster", ctypes.c_void_p),
+                ("olds_status", ctypes.c_void_p), ("olds_gen", ctypes.c_void_p), ("ver_gen", ctypes.c_void_p),
+                ("ver_flags", ctypes.c_void_p), ("ver_off", ctypes.c_void_p), ("st_off", ctypes.c_void_p)]
+
+
+class SyncFinView(ctypes.Structure):  # kad_sync_fin_view
+    _fields_ = [("out_ver_cluster", ctypes.c_void_p), ("out_ver_id", ctypes.c_void_p), ("ver_count", ctypes.c_void_p),
+                ("ver_write", ctypes.c_void_p), ("out_st_cluster", ctypes.c_void_p), ("out_st_status", ctypes.c_void_p),
+                ("out_st_gen", ctypes.c_void_p), ("st_count", ctypes.c_void_p), ("obj_out", ctypes.c_void_p),
+                ("reason_out", ctypes.c_void_p)]
+
+
 _lib = None
 
 
@@ -219,6 +250,8 @@ _CONSUMER_ABI = {
     "rollout": ("kad_rollout_plan", (ctypes.c_void_p,), (_I32, _I32, _I64, _I32, _I32), (_I32, _I32, _I32)),
     "dispatch": ("kad_dispatch_plan", (), (_I32, _I32, _I32), None),
     "policyrc": ("kad_policyrc_count", (), (_I32, _I64, _I32), (_I32,)),
+    "sync_needs_update": ("kad_sync_needs_update", (), (_I32, _I32), None),
+    "sync_finish": ("kad_sync_finish", (), (_I32, _I32, _I64, _I32), (_I32, _I32)),
 }
 
 
@@ -653,6 +686,76 @@ def policyrc_check(**arrays) -> int:
     return _check("policyrc", policyrc_args(**arrays))
 
 
+SYNC_NU_ROUTE = ("threads", "grid", "stride")
+SYNC_FIN_ROUTE = ("width", "long_min", "threads", "grid", "long_grid", "stride")
+
+
+def sync_needs_update_route_eval(n_rows: int, n_cu: int = 256) -> dict:
+    """kad_sync_needs_update_route_eval: the launch decision of a sync_needs_update (needs no GPU)."""
+    return _route_eval("sync_needs_update", SYNC_NU_ROUTE, n_rows, n_cu, error=KadError)
+
+
+def sync_finish_route_eval(n_objects: int, n_long: int, short_items: int, n_cu: int = 256) -> dict:
+    """kad_sync_finish_route_eval: the launch decision of a sync_finish (needs no GPU)."""
+    return _route_eval("sync_finish", SYNC_FIN_ROUTE, n_objects, n_long, short_items, n_cu, error=KadError)
+
+
+_SYNC_NU_IN = (("row_obj", np.int32), ("row_cluster", np.int32), ("row_target", np.int32), ("row_flags", np.uint8),
+               ("obj_flags", np.uint8), ("rec_off", np.int32), ("rec_cluster", np.int32), ("rec_version", np.int32),
+               ("ver_flags", np.uint8))
+_SYNC_NU_OUT = (("needs_update", np.uint8, 0), ("recorded", np.int32, 0))
+_SYNC_FIN_IN = (("obj_flags", np.uint16), ("reason_in", np.int32), ("cond_reason", np.int32), ("sel_off", np.int32),
+                ("sel_cluster", np.int32), ("ent_off", np.int32), ("ent_cluster", np.int32), ("ent_status", np.uint8),
+                ("ent_version", np.int32), ("oldv_off", np.int32), ("oldv_cluster", np.int32), ("oldv_version", np.int32),
+                ("olds_off", np.int32), ("olds_cluster", np.int32), ("olds_status", np.uint8), ("olds_gen", np.int64),
+                ("ver_gen", np.int64), ("ver_flags", np.uint8), ("ver_off", np.int64), ("st_off", np.int64))
+_SYNC_FIN_OUT = (("out_ver_cluster", np.int32, 1), ("out_ver_id", np.int32, 1), ("ver_count", np.int32, 0),
+                 ("ver_write", np.uint8, 0), ("out_st_cluster", np.int32, 2), ("out_st_status", np.uint8, 2),
+                 ("out_st_gen", np.int64, 2), ("st_count", np.int32, 0), ("obj_out", np.uint8, 0), ("reason_out", np.int32, 0))
+
+
+def sync_needs_update_args(n_clusters: int, **arrays):
+    """The kad_sync_nu_batch / kad_sync_nu_view of one call with the arrays that back them (the batch's fields by
+    name; the other counts are taken from obj_flags, row_flags and ver_flags as they are, so that a malformed batch
+    reaches the library's validation; ``n_versions`` overrides the last). Returns (batch, view, the input arrays, the
+    output arrays by name)."""
+    a = _flat(_SYNC_NU_IN, arrays)
+    n = lambda k: len(a[k]) if k in a else 0  # noqa: E731
+    counts = (int(n_clusters), n("obj_flags"), n("row_flags"), int(arrays.get("n_versions", n("ver_flags"))))
+    return _call_args(SyncNuBatch, SyncNuView, counts, _SYNC_NU_IN, _SYNC_NU_OUT, a, {0: counts[2]})
+
+
+def sync_needs_update_check(n_clusters: int, **arrays) -> int:
+    """kad_sync_needs_update_check: the call's validation of :func:`sync_needs_update_args` arguments; no GPU."""
+    return _check("sync_needs_update", sync_needs_update_args(n_clusters, **arrays))
+
+
+def sync_finish_args(n_clusters: int, n_reasons: int, reason_check_clusters: int, reason_ns_not_federated: int, **arrays):
+    """The kad_sync_fin_batch / kad_sync_fin_view of one call with the arrays that back them (the batch's fields by
+    name; n_objects and n_versions are taken from obj_flags and ver_flags as they are, so that a malformed batch
+    reaches the library's validation; ``n_versions`` overrides the second). Returns (batch, view, the input arrays,
+    the output arrays by name)."""
+    a = _flat(_SYNC_FIN_IN, arrays)
+    n = lambda k: len(a[k]) if k in a else 0  # noqa: E731
+    O = n("obj_flags")
+    counts = (int(n_clusters), O, int(arrays.get("n_versions", n("ver_flags"))), int(n_reasons),
+              int(reason_check_clusters), int(reason_ns_not_federated))
+
+    def cap(k):
+        off = a.get(k)
+        return int(off[-1]) if off is not None and len(off) == O + 1 and 0 <= int(off[-1]) < 2 ** 31 else 0
+
+    return _call_args(SyncFinBatch, SyncFinView, counts, _SYNC_FIN_IN, _SYNC_FIN_OUT, a,
+                      {0: O, 1: cap("ver_off"), 2: cap("st_off")})
+
+
+def sync_finish_check(n_clusters: int, n_reasons: int, reason_check_clusters: int, reason_ns_not_federated: int,
+                      **arrays) -> int:
+    """kad_sync_finish_check: kad_sync_finish's validation of :func:`sync_finish_args` arguments; no GPU."""
+    return _check("sync_finish", sync_finish_args(n_clusters, n_reasons, reason_check_clusters,
+                                                  reason_ns_not_federated, **arrays))
+
+
 class Context:
     """A kad_ctx: one HIP device, one stream, resident snapshot + batch."""
 
@@ -1046,6 +1149,43 @@ class Context:
     def policyrc_last_route(self) -> dict:
         """kad_policyrc_last_route: what the last policyrc_count() launched (policyrc_route_eval's record)."""
         return self._last_route("policyrc", POLICYRC_ROUTE)
+
+    def sync_needs_update(self, n_clusters: int, **arrays) -> dict:
+        """kad_sync_needs_update → {needs_update[n_rows], recorded[n_rows]}. Arguments as
+        :func:`sync_needs_update_args` (syncfin.SyncFinishBatch.needs_update_arrays())."""
+        return self._consume("kad_sync_needs_update", sync_needs_update_args(n_clusters, **arrays))
+
+    def sync_needs_update_timing(self):
+        """kad_sync_needs_update_timing: ms of the last sync_needs_update() — (inputs to the device,
+        syncfin_rows_kernel, outputs back)."""
+        return self._timing("sync_needs_update", 3)
+
+    def sync_needs_update_last_route(self) -> dict:
+        """kad_sync_needs_update_last_route: what the last sync_needs_update() launched."""
+        return self._last_route("sync_needs_update", SYNC_NU_ROUTE)
+
+    def sync_finish(self, n_clusters: int, n_reasons: int, reason_check_clusters: int, reason_ns_not_federated: int,
+                    **arrays) -> dict:
+        """kad_sync_finish → {out_ver_cluster, out_ver_id (object o's entries at ver_off[o] .. + ver_count[o]),
+        ver_count[O], ver_write[O], out_st_cluster, out_st_status, out_st_gen (at st_off[o] .. + st_count[o]),
+        st_count[O], obj_out[O], reason_out[O]}. Arguments as :func:`sync_finish_args`
+        (syncfin.SyncFinishBatch.finish_arrays())."""
+        return self._consume("kad_sync_finish", sync_finish_args(n_clusters, n_reasons, reason_check_clusters,
+                                                                 reason_ns_not_federated, **arrays))
+
+    def sync_finish_timing(self):
+        """kad_sync_finish_timing: ms of the last sync_finish() — (inputs to the device, syncfin_kernel, outputs
+        back)."""
+        return self._timing("sync_finish", 3)
+
+    def sync_finish_last_route(self) -> dict:
+        """kad_sync_finish_last_route: what the last sync_finish() launched (sync_finish_route_eval's record)."""
+        return self._last_route("sync_finish", SYNC_FIN_ROUTE)
+
+    def sync_finish_debug_route(self, width: int = 0, long_min: int = 0) -> None:
+        """kad_sync_finish_debug_route: the lane-group width and long_min of the following sync_finish() calls (0:
+        the route's own). Measurement and tests only."""
+        self._debug_route("sync_finish", width, long_min)
 
     def policyrc_debug_route(self, path: int = 0) -> None:
         """kad_policyrc_debug_route: the count kernel's path of the following policyrc_count() calls (0: the

@@ -1585,3 +1585,43 @@ def gen_dispatch(seed: int, W: int, C: int, placed: int = 5, observed: float = 0
                 ns_pl_off=ns_off.astype(np.int32), ns_cluster=np.concatenate(rows).astype(np.int32),
                 obj_ob_off=ob_off.astype(np.int32), ob_cluster=ob_cluster.astype(np.int32), ob_flags=ob_flags,
                 out_off=pl_off + ob_off)
+
+
+def gen_sync_finish(seed: int, W: int, C: int, touched: int, steady: float = 0.8):
+    """A synthetic sync-completion batch as kad_sync_finish's arrays (the arguments of Context.sync_finish, the four
+    scalars included): ``W`` federated objects over ``C`` joined clusters, each with ``touched`` dispatcher records
+    on ascending distinct clusters (a random start and stride). A share ``steady`` of the objects is in its steady
+    state: every record is an update that timed out into OK with the stored generation version, the stored
+    PropagatedVersion and ``status.clusters`` say the same and the condition is True, so nothing is to be written;
+    the others have one failed update in ten, a stored version list that lacks every third cluster, and a stored status that lacks its last cluster. Versions are interned
+    as ``gen:1`` .. ``gen:8`` and ``rv:1``; the selected clusters are the records' clusters."""
+    rng = np.random.default_rng([seed, 0x73796e])
+    touched = min(touched, C)
+    stride = np.maximum(1, rng.integers(1, max(2, C // max(touched, 1) + 1), W))
+    start = (rng.random(W) * (C - (touched - 1) * stride)).astype(np.int64) if touched else np.zeros(W, np.int64)
+    cl = (start[:, None] + np.arange(touched)[None, :] * stride[:, None]).astype(np.int32)  # [W, touched] ascending
+    ok = rng.random(W) < steady
+    ver = rng.integers(1, 10, (W, touched)).astype(np.int32)  # ids 1..8 gen:k, 9 rv:1
+    failed = (~ok[:, None]) & (rng.random((W, touched)) < 0.1)
+    ent_status = np.where(failed, 9, 21).astype(np.uint8)  # UpdateFailed / UpdateTimedOut
+    ent_version = np.where(failed, 0, ver).astype(np.int32)
+    off = (np.arange(W + 1) * touched).astype(np.int32)
+    # the stored versions: all of them (steady), or without every third and with two untouched clusters in front
+    keep_v = ok[:, None] | (np.arange(touched)[None, :] % 3 != 0)
+    oldv_n = keep_v.sum(1)
+    oldv_off = np.concatenate(([0], np.cumsum(oldv_n))).astype(np.int32)
+    keep_s = ok[:, None] | (np.arange(touched)[None, :] < touched - 1)
+    olds_off = np.concatenate(([0], np.cumsum(keep_s.sum(1)))).astype(np.int32)
+    gen = np.concatenate(([0], np.arange(1, 9), [0])).astype(np.int64)
+    flags = np.where(ok, 1 | 2 | 64 | 128, 1 | 2 | 16 | 64 | 128).astype(np.uint16)
+    ne, nv = np.full(W, touched, np.int64), oldv_n.astype(np.int64)
+    return {"n_clusters": C, "n_reasons": 3, "reason_check_clusters": 1, "reason_ns_not_federated": 2,
+            "obj_flags": flags, "reason_in": np.zeros(W, np.int32), "cond_reason": np.zeros(W, np.int32),
+            "sel_off": off, "sel_cluster": cl.reshape(-1), "ent_off": off, "ent_cluster": cl.reshape(-1),
+            "ent_status": ent_status.reshape(-1), "ent_version": ent_version.reshape(-1),
+            "oldv_off": oldv_off, "oldv_cluster": cl[keep_v], "oldv_version": ver[keep_v],
+            "olds_off": olds_off, "olds_cluster": cl[keep_s], "olds_status": np.ones(int(keep_s.sum()), np.uint8),
+            "olds_gen": gen[ver[keep_s]], "ver_gen": gen,
+            "ver_flags": np.array([0] + [3] * 8 + [1], np.uint8),
+            "ver_off": np.concatenate(([0], np.cumsum(ne + nv))).astype(np.int64),
+            "st_off": np.concatenate(([0], np.cumsum(ne))).astype(np.int64)}
