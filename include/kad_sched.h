@@ -371,8 +371,11 @@ int kad_snapshot_paths(kad_ctx* ctx, int32_t* out);
  *   [16] KAD_NO_ROWS (0), [17] KAD_ROWS_AFTER (0), [18] KAD_ROWS_NO_INLINE (0), [19] KAD_PREP_WAVE (1),
  *   [20] KAD_WIDE_MIN_NCH (5), [21] KAD_LEAN_BLOCKS_PER_CU (0: the occupancy query's answer) — the tuning
  *   variables of measurement builds, with the defaults every product build runs;
+ *   [22] every row table prep_kernel reads or writes starts on a 16-byte boundary (kad_schedule checks the
+ *   device pointers; 0 keeps prep_kernel's 8-byte accesses);
  * per_cu / row_per_cu stand for the occupancy queries of the main and the row kernel. out[KAD_ROUTE_FIELDS] is
- *   [0] prep kernel (0 prep_kernel, 1..3 prep_wave_kernel<2..4>),
+ *   [0] prep kernel (0 prep_kernel, 1..3 prep_wave_kernel<2..4>, 4 prep_kernel with 16-byte row accesses:
+ *   [22] set and a multiple of 4 chunks),
  *   [1] prep_kernel lanes per unit, [2] family (0 lean, 1 wide), [3] the main kernel's variant
  *   (kad_route_variant_name), [4] the row kernel's, [5] the defer pass's, [6] use_rows, [7] early_rows,
  *   [8] may_defer, [9] row kernel placement (0 none, 1 inside the wide kernel, 2 beside it, 3 after the main
@@ -382,7 +385,7 @@ int kad_snapshot_paths(kad_ctx* ctx, int32_t* out);
  * [15] compute units is the count of the first device the process scheduled on, whichever device ctx is on.
  * kad_last_route: the same record for what the last kad_schedule launched (KAD_ESTATE before one).
  * Measurement / tests only. No reference counterpart. */
-#define KAD_ROUTE_IN_FIELDS 22
+#define KAD_ROUTE_IN_FIELDS 23
 #define KAD_ROUTE_FIELDS 21
 int kad_route_eval(const int32_t* in, int32_t per_cu, int32_t row_per_cu, int32_t* out);
 int kad_last_route(kad_ctx* ctx, int32_t* out);

@@ -1129,6 +1129,9 @@ static int schedule_locked(kad_ctx* c, const kad_profile* p, uint8_t* dbg_feas, 
              (int32_t)p->filter_mask, (int32_t)p->score_mask,
              dbg_feas || dbg_total, c->side && c->fork_ev && c->join_ev, n_cus()};
   route_tuning(in);
+  in.rows16 = rows_aligned16({c->bd.req_mask, c->bd.sw, c->bd.cw, c->sd.fitfold ? c->sd.fit_rows[0] : nullptr,
+                              c->sd.fitfold ? c->sd.fit_rows[1] : nullptr, c->sd.fold ? c->sd.taint_tab : nullptr,
+                              c->sd.fold ? c->sd.slices : nullptr});
   Route& rt = c->route;
   rt = route_schedule(in);
   c->bd.use_rows = rt.use_rows;

@@ -7,6 +7,25 @@
 
 namespace kad {
 
+// Words i .. i+CPL-1 of `base` as CPL/2 16-byte accesses. Only on the PREP_VEC route (kad_route.h): the host
+// launches it where nch % PREP_CPL == 0 (no lane has a clamped tail, and every row offset is a multiple of
+// CPL words) and every base is 16-byte aligned, so i is even and the address a multiple of 16.
+template <int CPL>
+__device__ __forceinline__ void ld_words(const uint64_t* base, uint32_t i, uint64_t (&r)[CPL]) {
+  static_assert(CPL % 2 == 0, "16-byte accesses hold two words");
+  ulonglong2 v[CPL / 2];
+#pragma unroll
+  for (int k = 0; k < CPL / 2; k++) v[k] = ldg(reinterpret_cast<const ulonglong2*>(base), (i >> 1) + (uint32_t)k);
+#pragma unroll
+  for (int k = 0; k < CPL / 2; k++) r[2 * k] = v[k].x, r[2 * k + 1] = v[k].y;
+}
+template <int CPL>
+__device__ __forceinline__ void st_words(uint64_t* p, const uint64_t (&r)[CPL]) {
+  static_assert(CPL % 2 == 0, "16-byte accesses hold two words");
+#pragma unroll
+  for (int k = 0; k < CPL / 2; k++) reinterpret_cast<ulonglong2*>(p)[k] = make_ulonglong2(r[2 * k], r[2 * k + 1]);
+}
+
 // One lane per (unit, PREP_CPL consecutive 64-cluster chunks), every launch,
 // before the schedule kernel:
 //  * the unit's first lanes write its 64-B UnitRec (16 B each), routing units that use a
@@ -23,8 +42,9 @@ namespace kad {
 // critical path in the schedule kernel.
 // p(i): word i of the unit's filter program (prep_kernel stages the first words in LDS). The CPL
 // chunks ch0 .. ch0+CPL-1 are evaluated together (their row loads are independent); chunks past
-// nch read chunk nch-1 and are never stored.
-template <int CPL, class Prog, bool WAVE_ANY = false>
+// nch read chunk nch-1 and are never stored. VEC (prep_kernel<true>): no chunk is past nch and a row's CPL
+// words are read as 16-byte loads (ld_words).
+template <int CPL, class Prog, bool WAVE_ANY = false, bool VEC = false>
 __device__ __forceinline__ void affinity_words(const uint64_t* rows, Prog p, uint32_t nch, uint32_t ch0,
                                                uint64_t (&out)[CPL], uint32_t cst = 1) {
   uint32_t cc[CPL];
@@ -32,8 +52,12 @@ __device__ __forceinline__ void affinity_words(const uint64_t* rows, Prog p, uin
   for (int k = 0; k < CPL; k++) cc[k] = ch0 + k * cst < nch ? ch0 + k * cst : nch - 1;
   auto and_row = [&](uint64_t (&v)[CPL], int id) {
     uint64_t r[CPL];
+    if constexpr (VEC) {
+      ld_words<CPL>(rows, (uint32_t)id * nch + ch0, r);
+    } else {
 #pragma unroll
-    for (int k = 0; k < CPL; k++) r[k] = ldg(rows, (uint32_t)id * nch + cc[k]);
+      for (int k = 0; k < CPL; k++) r[k] = ldg(rows, (uint32_t)id * nch + cc[k]);
+    }
 #pragma unroll
     for (int k = 0; k < CPL; k++) v[k] &= r[k];
   };
@@ -195,8 +219,8 @@ __global__ __launch_bounds__(256) void taint_table_kernel(SnapDev s, uint64_t* t
 // unit w on chunks cc[0..CPL) (TW <= TFOLD_MAX_TW): clusters with a NoSchedule|NoExecute taint the unit
 // does not tolerate are out — only NoExecute ones on its CurrentClusters (cw) — and clusters without its
 // GVK. The untolerated present taints are looked up 8 ids at a time in SnapDev::taint_tab, each lookup
-// serving the lane's CPL chunks (independent loads).
-template <int CPL>
+// serving the lane's CPL chunks (independent loads). VEC: cc[k] = cc[0] + k, read as 16-byte loads.
+template <int CPL, bool VEC = false>
 __device__ __forceinline__ void folded_words(const SnapDev& s, uint32_t fm, uint32_t f, int gvk, const uint64_t* tol,
                                              const uint64_t (&cw)[CPL], uint32_t nch, const uint32_t (&cc)[CPL],
                                              uint64_t (&out)[CPL]) {
@@ -217,14 +241,22 @@ __device__ __forceinline__ void folded_words(const SnapDev& s, uint32_t fm, uint
         if (sub) {
           const uint64_t* rn = s.taint_tab + ((size_t)(8 * tw + gi) * 256 + sub) * nch;
           uint64_t x[CPL];
+          if constexpr (VEC) {
+            ld_words<CPL>(rn, cc[0], x);
+          } else {
 #pragma unroll
-          for (int k = 0; k < CPL; k++) x[k] = rn[cc[k]];
+            for (int k = 0; k < CPL; k++) x[k] = rn[cc[k]];
+          }
 #pragma unroll
           for (int k = 0; k < CPL; k++) bad_ns[k] |= x[k];
           if (cur) {
             const uint64_t* re = s.taint_tab + ((ng + 8 * tw + gi) * 256 + sub) * nch;
+            if constexpr (VEC) {
+              ld_words<CPL>(re, cc[0], x);
+            } else {
 #pragma unroll
-            for (int k = 0; k < CPL; k++) x[k] = re[cc[k]];
+              for (int k = 0; k < CPL; k++) x[k] = re[cc[k]];
+            }
 #pragma unroll
             for (int k = 0; k < CPL; k++) bad_ne[k] |= x[k];
           }
@@ -237,8 +269,15 @@ __device__ __forceinline__ void folded_words(const SnapDev& s, uint32_t fm, uint
   if (fm & (1u << KAD_PL_API_RESOURCES)) {  // any GVK id of the snapshot's GW words (-1: no cluster has it)
     const bool has = gvk >= 0 && gvk < 64 * s.GW;
     const uint64_t* rg = s.slices + ((size_t)128 * s.TW + (has ? gvk : 0)) * nch;
+    if constexpr (VEC) {
+      uint64_t x[CPL];
+      ld_words<CPL>(rg, cc[0], x);
 #pragma unroll
-    for (int k = 0; k < CPL; k++) out[k] &= has ? rg[cc[k]] : 0ull;
+      for (int k = 0; k < CPL; k++) out[k] &= has ? x[k] : 0ull;
+    } else {
+#pragma unroll
+      for (int k = 0; k < CPL; k++) out[k] &= has ? rg[cc[k]] : 0ull;
+    }
   }
 }
 
@@ -264,7 +303,11 @@ __device__ __forceinline__ int2 fit_ranks(const SnapDev& s, const int64_t (*fenc
 #ifndef KAD_PREP_MINW
 #define KAD_PREP_MINW 1
 #endif
-__global__ __launch_bounds__(256, KAD_PREP_MINW) void prep_kernel(SnapDev s, BatchDev b, ProfDev p, int force_full) {
+// VEC (route PREP_VEC, decided per launch on the host: nch % PREP_CPL == 0 and req_mask, fit_rows, taint_tab,
+// slices, sw and cw all 16-byte aligned): every lane owns CPL whole chunks, and the CPL words of each row it
+// reads or stores are moved as 16-byte accesses — the same bytes in half the vector memory instructions.
+template <bool VEC>
+__global__ __launch_bounds__(256, VEC ? 5 : KAD_PREP_MINW) void prep_kernel(SnapDev s, BatchDev b, ProfDev p, int force_full) {
   constexpr int CPL = PREP_CPL;
   __shared__ int32_t prog_words[256 * CPL];  // words CPL*l .. CPL*l+CPL-1 of its unit's filter program, per lane
   const uint32_t nch = (uint32_t)((s.C + 63) >> 6);
@@ -344,16 +387,24 @@ __global__ __launch_bounds__(256, KAD_PREP_MINW) void prep_kernel(SnapDev s, Bat
         const int t = base + i;
         return (i < (int)(per * CPL) && t >= 0 && t < 256 * CPL) ? prog_words[t] : gp[i];
       };
-      affinity_words<CPL>(b.req_mask, word, nch, ch0, m);
+      affinity_words<CPL, decltype(word), false, VEC>(b.req_mask, word, nch, ch0, m);
     }
     if (s.fitfold && (fm & (1u << KAD_PL_CLUSTER_RESOURCES_FIT)) && (f & KAD_W_FIT_NONZERO)) {
       // fit.go:73-134 (cpu, memory) by threshold rows: clusters whose available amount >= the request
       const int2 j = fit_ranks(s, fences, rqc, rqm);
       const int jc = j.x, jm = j.y;
+      if constexpr (VEC) {
+        uint64_t rc[CPL], rm[CPL];
+        ld_words<CPL>(s.fit_rows[0], (uint32_t)jc * nch + ch0, rc);
+        ld_words<CPL>(s.fit_rows[1], (uint32_t)jm * nch + ch0, rm);
 #pragma unroll
-      for (int k = 0; k < CPL; k++) {
-        const uint32_t ch = ch0 + k < nch ? ch0 + k : nch - 1;
-        m[k] &= ldg(s.fit_rows[0], (uint32_t)jc * nch + ch) & ldg(s.fit_rows[1], (uint32_t)jm * nch + ch);
+        for (int k = 0; k < CPL; k++) m[k] &= rc[k] & rm[k];
+      } else {
+#pragma unroll
+        for (int k = 0; k < CPL; k++) {
+          const uint32_t ch = ch0 + k < nch ? ch0 + k : nch - 1;
+          m[k] &= ldg(s.fit_rows[0], (uint32_t)jc * nch + ch) & ldg(s.fit_rows[1], (uint32_t)jm * nch + ch);
+        }
       }
     }
     const bool place = (fm & (1u << KAD_PL_PLACEMENT_FILTER)) && (f & KAD_W_HAS_PLACEMENT);
@@ -375,18 +426,26 @@ __global__ __launch_bounds__(256, KAD_PREP_MINW) void prep_kernel(SnapDev s, Bat
       tw[0] = tol0;
       for (int t = 1; t < s.TW && t < TFOLD_MAX_TW; t++) tw[t] = b.tol_all[(size_t)tolset * b.TW + t];
       uint64_t fw[CPL];
-      folded_words<CPL>(s, fm, f, gvk, tw, cwv, nch, cc, fw);
+      folded_words<CPL, VEC>(s, fm, f, gvk, tw, cwv, nch, cc, fw);
 #pragma unroll
       for (int k = 0; k < CPL; k++) m[k] &= fw[k];
     }
+    if constexpr (VEC) {  // chunks ch0 .. ch0+CPL-1 all exist
+      if (ch0 + CPL == nch && (s.C & 63)) m[CPL - 1] &= (1ull << (s.C & 63)) - 1;  // clusters past C: never feasible
+      if (curw) st_words<CPL>(b.cw + (size_t)w * nch + ch0, cwv);
+      st_words<CPL>(b.sw + (size_t)w * nch + ch0, m);
 #pragma unroll
-    for (int k = 0; k < CPL; k++) {
-      const uint32_t ch = ch0 + k;
-      if (ch >= nch) break;
-      if (curw) b.cw[(size_t)w * nch + ch] = cwv[k];
-      if (ch == nch - 1 && (s.C & 63)) m[k] &= (1ull << (s.C & 63)) - 1;  // clusters past C: never feasible
-      b.sw[(size_t)w * nch + ch] = m[k];
-      cnt += popc64(m[k]);
+      for (int k = 0; k < CPL; k++) cnt += popc64(m[k]);
+    } else {
+#pragma unroll
+      for (int k = 0; k < CPL; k++) {
+        const uint32_t ch = ch0 + k;
+        if (ch >= nch) break;
+        if (curw) b.cw[(size_t)w * nch + ch] = cwv[k];
+        if (ch == nch - 1 && (s.C & 63)) m[k] &= (1ull << (s.C & 63)) - 1;  // clusters past C: never feasible
+        b.sw[(size_t)w * nch + ch] = m[k];
+        cnt += popc64(m[k]);
+      }
     }
   }
   // early_rows: in the wide kernel's FITF mode (fold + fitfold) the static words are the whole filter, so

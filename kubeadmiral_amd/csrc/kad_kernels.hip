@@ -123,8 +123,8 @@ hipError_t launch_slices(const SnapDev& s, uint64_t* slices, hipStream_t st) {
 
 // The prep and schedule kernels by route id (kad_route.h: PREP*, KAD_VARIANTS): the one list of their
 // instantiations, for the LDS attribute, the occupancy queries and the launches.
-static void (*const PREP_FN[4])(SnapDev, BatchDev, ProfDev, int) = {prep_kernel, prep_wave_kernel<2>, prep_wave_kernel<3>,
-                                                                    prep_wave_kernel<4>};
+static void (*const PREP_FN[PREP_COUNT])(SnapDev, BatchDev, ProfDev, int) = {
+    prep_kernel<false>, prep_wave_kernel<2>, prep_wave_kernel<3>, prep_wave_kernel<4>, prep_kernel<true>};
 #define X(n, ...) (const void*)__VA_ARGS__,
 static const void* const VARIANT_FN[KV_COUNT] = {KAD_VARIANTS(X)};
 #undef X
@@ -141,7 +141,8 @@ hipError_t launch_prep(const SnapDev& s, const BatchDev& b, const ProfDev& p, bo
   (void)hipGetLastError();
   // prep_kernel: prep_lanes lanes per unit; prep_wave_kernel: one unit per wave (not persistent: C5's prep is
   // L2-miss bound and took 587 -> 729 us with the resident grid, profiles/r06/ab_c5_prep_persistent.txt)
-  const long grid = r.prep == PREP ? ((long)b.W * r.prep_lanes + 255) / 256 : ((long)b.W + 3) / 4;
+  if (r.prep < 0 || r.prep >= PREP_COUNT) return hipErrorInvalidValue;
+  const long grid = r.prep == PREP || r.prep == PREP_VEC ? ((long)b.W * r.prep_lanes + 255) / 256 : ((long)b.W + 3) / 4;
   // (one block at W = 0 still resets defer_n)
   hipLaunchKernelGGL(PREP_FN[r.prep], dim3((unsigned)(grid > 0 ? grid : 1)), dim3(256), 0, st, s, b, p, force_full ? 1 : 0);
   return hipGetLastError();

@@ -4,6 +4,8 @@
 #pragma once
 #include "../../include/kad_sched.h"
 #include "kad_layout.h"
+#include <cstdint>
+#include <initializer_list>
 
 namespace kad {
 
@@ -17,6 +19,9 @@ struct RouteIn {
   // tuning (tuning_env: measurement builds only): KAD_NO_ROWS, KAD_ROWS_AFTER, KAD_ROWS_NO_INLINE, KAD_PREP_WAVE,
   // KAD_WIDE_MIN_NCH, KAD_LEAN_BLOCKS_PER_CU (< 1: as many lean blocks per CU as the occupancy query answers)
   int32_t no_rows = 0, rows_after = 0, rows_no_inline = 0, prep_wave = 1, wide_min_nch = 5, lean_blocks_per_cu = 0;
+  // the rows prep_kernel reads and writes all start on 16-byte boundaries (rows_aligned16 of BatchDev::req_mask, sw,
+  // cw and SnapDev::fit_rows, taint_tab, slices): with whole lanes (nch % PREP_CPL == 0) the PREP_VEC route
+  int32_t rows16 = 0;
 };
 static_assert(sizeof(RouteIn) == 4 * KAD_ROUTE_IN_FIELDS, "RouteIn is a flat int32 record");
 
@@ -53,7 +58,7 @@ inline const char* variant_name(int v) {
 #undef X
   return v >= 0 && v < KV_COUNT ? names[v] : "?";
 }
-enum : int32_t { PREP = 0, PREP_WAVE2, PREP_WAVE3, PREP_WAVE4 };
+enum : int32_t { PREP = 0, PREP_WAVE2, PREP_WAVE3, PREP_WAVE4, PREP_VEC, PREP_COUNT };  // PREP_VEC: prep_kernel<true>
 enum : int32_t { FAMILY_LEAN = 0, FAMILY_WIDE };
 enum : int32_t { ROWS_NONE = 0, ROWS_INLINE, ROWS_BESIDE, ROWS_AFTER };
 
@@ -76,6 +81,16 @@ static_assert(sizeof(Route) == 4 * KAD_ROUTE_FIELDS, "Route is a flat int32 reco
 inline int route_nch(int C) { return (C + 63) >> 6; }
 // prep_kernel lanes per unit (a power of two <= 64 lets it count a unit's feasible clusters in one wave)
 inline int prep_lanes_per_unit(int C) { return C > 0 ? (route_nch(C) + PREP_CPL - 1) / PREP_CPL : 1; }
+// RouteIn::rows16: 1 if every address is a multiple of 16 bytes (a null pointer, a table this snapshot or batch
+// does not have, is never read and counts as aligned)
+inline int32_t rows_aligned16(std::initializer_list<const void*> bases) {
+  uintptr_t any = 0;
+  for (const void* p : bases) any |= reinterpret_cast<uintptr_t>(p);
+  return (any & 15) == 0;
+}
+// prep_kernel's 16-byte row accesses need every lane to own PREP_CPL whole chunks (so a row's words at a lane
+// are PREP_CPL consecutive ones at a multiple of PREP_CPL, no clamped tail) and 16-byte aligned bases
+inline bool prep_vec_ok(int nch, int rows16) { return PREP_CPL % 2 == 0 && nch > 0 && nch % PREP_CPL == 0 && rows16 != 0; }
 // the wide kernel takes clean snapshots with min_nch <= nch <= WIDE_MAX_NCH
 // (KAD_WIDE_MIN_NCH overrides the lower bound, for A/B runs of C <= 256)
 inline bool route_wide(int C, int clean, int min_nch) {
@@ -90,7 +105,7 @@ inline Route route_schedule(const RouteIn& in) {
   const int nch = route_nch(in.C);
   // wide snapshots (more than 64 chunks, up to 256): prep takes one unit per wave
   const int cw = (nch + 63) / 64;
-  r.prep = (nch > 64 && cw <= 4 && in.prep_wave) ? PREP_WAVE2 + (cw - 2) : PREP;
+  r.prep = (nch > 64 && cw <= 4 && in.prep_wave) ? PREP_WAVE2 + (cw - 2) : (prep_vec_ok(nch, in.rows16) ? PREP_VEC : PREP);
   const int per = r.prep_lanes = prep_lanes_per_unit(in.C);
   const bool wide = route_wide(in.C, in.clean, in.wide_min_nch);
   // long feasible lists go to schedule_row_kernel when every filter is in the static words

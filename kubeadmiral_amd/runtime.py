@@ -206,11 +206,11 @@ def declared_functions() -> List[str]:
 # kad_route_eval's records (include/kad_sched.h): the inputs with the defaults of the tuning fields, the outputs
 ROUTE_IN = dict(C=0, clean=0, fold=0, fitfold=0, TW=1, snap_negative=0, W=1, has_current=0, zero_req=0, batch_defer=0,
                 batch_many_terms=0, filter_mask=0, score_mask=0, debug_capture=0, side_stream=1, n_cu=256, no_rows=0,
-                rows_after=0, rows_no_inline=0, prep_wave=1, wide_min_nch=5, lean_blocks_per_cu=0)
+                rows_after=0, rows_no_inline=0, prep_wave=1, wide_min_nch=5, lean_blocks_per_cu=0, rows16=0)
 ROUTE_OUT = ("prep", "prep_lanes", "family", "variant", "row_variant", "full_variant", "use_rows", "early_rows",
              "may_defer", "rows", "defer_pass", "cache_ne", "cache_pn", "cache_zs", "wpb", "threads", "lds", "wave_bytes",
              "grid", "batch", "row_grid")
-_ROUTE_ENUMS = {"prep": ("PREP", "PREP_WAVE2", "PREP_WAVE3", "PREP_WAVE4"), "family": ("LEAN", "WIDE"),
+_ROUTE_ENUMS = {"prep": ("PREP", "PREP_WAVE2", "PREP_WAVE3", "PREP_WAVE4", "PREP_VEC"), "family": ("LEAN", "WIDE"),
                 "rows": ("NONE", "INLINE", "BESIDE", "AFTER")}
 
 

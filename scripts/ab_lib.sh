@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B of two builds of libkad.so on the same box: bench lines alternating between the product library and
-# ablibs/libkad_old.so (runtime.LIB_PATH patched before the first load).
+# ablibs/libkad_old.so (loaded before anything else asks for the library).
 #   scripts/ab_lib.sh TAG "c3 c2" [rounds]
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
@@ -12,8 +12,8 @@ for r in $(seq 1 $rounds); do
 import os, runpy, sys
 lib, cfg = sys.argv[1], sys.argv[2]
 from kubeadmiral_amd import runtime
-if lib == "old":
-    runtime.LIB_PATH = os.path.join(os.path.dirname(os.path.dirname(runtime.__file__)), "ablibs", "libkad_old.so")
+if lib == "old":  # (load_library's default path is bound at its definition: load the file itself, later calls return it)
+    runtime.load_library(os.path.join(os.path.dirname(os.path.dirname(runtime.__file__)), "ablibs", "libkad_old.so"))
 sys.argv = ["bench.py", "--config", cfg, "--steps", "20", "--warmup", "3", "--full", "--no-cpu-baseline", "--no-extra",
             "--no-sweep", "--no-e2e"]
 runpy.run_path("bench.py", run_name="__main__")
