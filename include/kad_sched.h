@@ -1433,6 +1433,172 @@ int kad_sync_finish_last_route(kad_ctx* ctx, int32_t* out);
  * own) of the following kad_sync_finish calls. */
 int kad_sync_finish_debug_route(kad_ctx* ctx, int32_t force_width, int32_t force_long_min);
 
+/* ------------------------------------------------------ monitor: per-object sync and status meters, their report
+ * The monitor controller (pkg/controllers/monitor) keeps one BaseMeter per federated object (monitor_controller.go:
+ * 75-82), updates it on every object event (MonitorSubController.reconcile, monitor_subcontroller.go:172-343) and
+ * walks all of them every ReportInterval (DoReport, report.go:31-163). The meters are the one consumer state that
+ * stays on the device between calls: a table of slots, one per meter, a column per field (creation, last_update,
+ * sync_success, last_status_synced as times, out_of_sync_ns as a duration, the interned kind type_id = the text before
+ * the first '/' of the meter key, flags with KAD_MON_LIVE). The caller maps meter keys to slots, interns kinds and
+ * cluster names, and keeps every meter's lastStatus map; the device says when to replace one.
+ *
+ * Time: int64 nanoseconds since the Unix epoch, a real time in [0, 2^62). Go's zero time.Time is KAD_MON_TIME_ZERO
+ * (-2^62); a time derived from it by Add is KAD_MON_TIME_ZERO plus the duration (all such values lie below -2^61 and
+ * order as Go orders them). After is >, IsZero is == KAD_MON_TIME_ZERO, and Sub saturates at MinInt64 / MaxInt64
+ * whenever exactly one operand lies below -2^61, as Go's does for operands more than 292 years apart. `now` is always
+ * an argument and a real time.
+ *
+ * kad_monitor_reserve grows the table to at least `capacity` slots and keeps its contents (it never shrinks);
+ * kad_monitor_load writes n slots (distinct, in [0, capacity)) from the caller's columns, kad_monitor_read reads n
+ * slots back (any array of either may be null: that column is left alone / not returned; load's times must be real,
+ * or within 2^60 of KAD_MON_TIME_ZERO; flags only KAD_MON_LIVE; type_id >= 0); kad_monitor_clear empties the table
+ * and keeps its capacity; kad_monitor_info: out[0] capacity, out[1] n_slots = one past the highest slot ever written
+ * since the last clear (what the report walks), out[2] the live slots, out[3] the highest type id stored, -1 without.
+ *
+ * kad_monitor_reconcile: a batch of n_objects events, slot[i] distinct within the call (the reference's worker
+ * serialises per key: a caller whose batch repeats a key splits it into successive calls). obj_flags[i] carries what
+ * the caller read from strings: KAD_MON_OBJ_DELETED (the object is absent or has a deletionTimestamp: the meter is
+ * deleted and nothing else happens, :182-191), _NEW (no meter yet: creation_ns[i], KAD_MON_TIME_ZERO without a
+ * creationTimestamp, starts one; it must agree with the slot's LIVE flag), _SS_PARSED (the syncSuccessTimestamp
+ * annotation parsed: sync_success_ns[i]; an absent or unparsable one keeps the meter's value, :257-262),
+ * _LASTGEN_PRESENT / _LASTGEN_EQUAL and _LSSG_PRESENT / _LSSG_EQUAL (the lastGeneration / lastSyncSuccessGeneration
+ * annotation exists / equals strconv.FormatInt(generation) as a string, :266-293), _STATUS_ENABLED (the type config's,
+ * :210), _STATUS_ABSENT (the status object is absent or being deleted, :216-224), _FED_MISSING (a clusterStatus entry
+ * lacks clusterName or status.observedGeneration: ErrMissingObservedGenerationField, checked before the member
+ * clusters, :388-402), _CLUSTER_ERR (a member object lacks status.observedGeneration, :418-429), _HAS_LAST (the
+ * meter's lastStatus is not nil, which an empty map is not). Three CSR lists of (cluster id, observedGeneration) per
+ * object, each strictly ascending by cluster id (the caller dedupes, the later of two equal names winning as in the
+ * Go map): fed (the status object's clusterStatus), mem (the member clusters' objects), last (the meter's lastStatus).
+ * reflect.DeepEqual of two such maps is "same length and equal entry by entry".
+ * Outputs per object: result[i] (KAD_MON_RESULT_ALL_OK, _STATUS_ERROR, _REQUEUE = worker.Result{RequeueAfter: 5 s});
+ * bits[i]: KAD_MON_BIT_METER_DELETED, _UPDATE_ANNOTATION (write lastGeneration = generation, :295-298),
+ * _STATUS_STORED (the status half was stored: the second meters.Store, :250), _REPLACE_LAST (the stored lastStatus
+ * becomes this call's mem list), _MISSING_OBSERVED_GENERATION, _LOG_LAST_CLUSTER (the log line's lastStatus is the mem
+ * list); meter[i][5] = the slot's five columns after the call (zeros for a deleted meter); would[i][2] = the log
+ * line's lastStatusSyncedTimestamp and outOfSyncDuration (:228-249). On ErrStatusOutOfSync the reference has changed
+ * its local copy of the meter and returns without storing it (:236-237): would[] and _LOG_LAST_CLUSTER carry those
+ * values, the slot's status columns stay as they were.
+ * One launch (monitor_reconcile_kernel: a lane group per object, the two DeepEquals as strided compares and a ballot,
+ * the group's lane 0 runs the state machine and writes the slot in place). Validated on the host first (KAD_EINVAL;
+ * more than KAD_DISPATCH_MAX_CLUSTERS clusters: KAD_EUNSUPPORTED; a slot at or beyond the capacity: KAD_ENOSPC).
+ *
+ * kad_monitor_report: DoReportLatencyCount, DoReportSyncLatency and DoReportStatusLatency at now_ns over slots
+ * [0, n_slots). counters[14]: [0..5] the latency5min, 10min, 30min, 1hour, 6hour (180 minutes as in the reference) and
+ * 1day counts, [6..11] their .status counts (counted inside start.After(syncSuccessTimestamp), as report.go:112-141
+ * does), [12] totalsync.throughput, [13] totalstatus.throughput; type_sync[n_types] / type_status[n_types] the
+ * typelatency5min.count / .status.count per type id (the reference emits the non-zero ones); the timer lists
+ * (slot, Milliseconds()) of totalsync.latency.ms and totalstatus.latency.ms in ascending slot order, n_timers[2]
+ * their lengths. A list longer than timer_cap: KAD_ENOSPC with n_timers and everything else filled in and the first
+ * timer_cap entries of the list. n_types must exceed every stored type id. Integer atomics only: nothing depends on an
+ * order. Neither call reads or writes state that kad_schedule uses; a kad_group member accepts them.
+ * A call that fails its validation changes nothing. The host's record of the table (the LIVE flags that _NEW is
+ * checked against, n_slots, the highest type id) follows a call only once its kernel and copies have completed: after
+ * a KAD_EHIP from kad_monitor_reconcile or kad_monitor_load the device table and that record may disagree, and the
+ * table is to be emptied (kad_monitor_clear) and loaded again before it is used. */
+#define KAD_MON_TIME_ZERO (-(1ll << 62))
+#define KAD_MON_LIVE 1u
+#define KAD_MON_OBJ_DELETED 1u
+#define KAD_MON_OBJ_NEW 2u
+#define KAD_MON_OBJ_SS_PARSED 4u
+#define KAD_MON_OBJ_LASTGEN_PRESENT 8u
+#define KAD_MON_OBJ_LASTGEN_EQUAL 16u
+#define KAD_MON_OBJ_LSSG_PRESENT 32u
+#define KAD_MON_OBJ_LSSG_EQUAL 64u
+#define KAD_MON_OBJ_STATUS_ENABLED 128u
+#define KAD_MON_OBJ_STATUS_ABSENT 256u
+#define KAD_MON_OBJ_FED_MISSING 512u
+#define KAD_MON_OBJ_CLUSTER_ERR 1024u
+#define KAD_MON_OBJ_HAS_LAST 2048u
+#define KAD_MON_RESULT_ALL_OK 0
+#define KAD_MON_RESULT_STATUS_ERROR 1
+#define KAD_MON_RESULT_REQUEUE 2
+#define KAD_MON_BIT_METER_DELETED 1u
+#define KAD_MON_BIT_UPDATE_ANNOTATION 2u
+#define KAD_MON_BIT_STATUS_STORED 4u
+#define KAD_MON_BIT_REPLACE_LAST 8u
+#define KAD_MON_BIT_MISSING_OBSERVED_GENERATION 16u
+#define KAD_MON_BIT_LOG_LAST_CLUSTER 32u
+int kad_monitor_reserve(kad_ctx* ctx, int64_t capacity);
+int kad_monitor_load(kad_ctx* ctx, int32_t n, const int32_t* slots, const int64_t* creation, const int64_t* last_update,
+                     const int64_t* sync_success, const int64_t* last_status_synced, const int64_t* out_of_sync_ns,
+                     const int32_t* type_id, const uint8_t* flags);
+int kad_monitor_read(kad_ctx* ctx, int32_t n, const int32_t* slots, int64_t* creation, int64_t* last_update,
+                     int64_t* sync_success, int64_t* last_status_synced, int64_t* out_of_sync_ns, int32_t* type_id,
+                     uint8_t* flags);
+int kad_monitor_clear(kad_ctx* ctx);
+int kad_monitor_info(kad_ctx* ctx, int64_t out[4]);
+typedef struct kad_monitor_batch {
+  int32_t n_objects;
+  int32_t n_clusters;
+  int64_t now_ns;
+  const int32_t* slot;            /* [n_objects] distinct */
+  const uint16_t* obj_flags;      /* [n_objects] KAD_MON_OBJ_* */
+  const int32_t* type_id;         /* [n_objects] >= 0 */
+  const int64_t* creation_ns;     /* [n_objects] read with _NEW */
+  const int64_t* sync_success_ns; /* [n_objects] read with _SS_PARSED */
+  const int32_t* fed_off;         /* [n_objects + 1] */
+  const int32_t* fed_cluster;
+  const int64_t* fed_gen;
+  const int32_t* mem_off;         /* [n_objects + 1] */
+  const int32_t* mem_cluster;
+  const int64_t* mem_gen;
+  const int32_t* last_off;        /* [n_objects + 1] */
+  const int32_t* last_cluster;
+  const int64_t* last_gen;
+} kad_monitor_batch;
+typedef struct kad_monitor_view {
+  uint8_t* result; /* [n_objects] KAD_MON_RESULT_* */
+  uint8_t* bits;   /* [n_objects] KAD_MON_BIT_* */
+  int64_t* meter;  /* [n_objects][5] */
+  int64_t* would;  /* [n_objects][2] */
+} kad_monitor_view;
+int kad_monitor_reconcile(kad_ctx* ctx, const kad_monitor_batch* batch, const kad_monitor_view* out);
+/* Host only (no device, no ctx): the same validation, except what needs the table (a slot's capacity and LIVE flag). */
+int kad_monitor_reconcile_check(const kad_monitor_batch* batch, const kad_monitor_view* out);
+/* ms[0] = the inputs' copies to the device, ms[1] = monitor_reconcile_kernel, ms[2] = the outputs' copies back. */
+int kad_monitor_reconcile_timing(kad_ctx* ctx, float ms[3]);
+/* The launch decision (csrc/kad_monitor.h route_monitor_reconcile; no device work, no ctx): n_long objects with a
+ * list of more than long_min entries, short_items = the other objects' longest lists summed.
+ * out[KAD_MON_REC_ROUTE_FIELDS] is [0] the lane-group width, [1] long_min, [2] block threads, [3] group-path blocks,
+ * [4] long-path blocks, [5] the objects between two of one group. */
+#define KAD_MON_REC_ROUTE_FIELDS 6
+int kad_monitor_reconcile_route_eval(int32_t n_objects, int32_t n_long, int64_t short_items, int32_t n_cu, int32_t* out);
+int kad_monitor_reconcile_last_route(kad_ctx* ctx, int32_t* out);
+/* Measurement and tests only: the lane-group width (0, or a power of two in [1, 64]) and long_min (0: the route's own)
+ * of the following kad_monitor_reconcile calls. */
+int kad_monitor_reconcile_debug_route(kad_ctx* ctx, int32_t force_width, int32_t force_long_min);
+typedef struct kad_monitor_report_batch {
+  int64_t now_ns;
+  int32_t n_types;
+  int32_t timer_cap; /* entries either timer list holds */
+} kad_monitor_report_batch;
+typedef struct kad_monitor_report_view {
+  int32_t* counters;    /* [14] */
+  int32_t* type_sync;   /* [n_types] */
+  int32_t* type_status; /* [n_types] */
+  int32_t* sync_slot;   /* [timer_cap] */
+  int64_t* sync_ms;     /* [timer_cap] */
+  int32_t* status_slot; /* [timer_cap] */
+  int64_t* status_ms;   /* [timer_cap] */
+  int32_t* n_timers;    /* [2] */
+} kad_monitor_report_view;
+int kad_monitor_report(kad_ctx* ctx, const kad_monitor_report_batch* batch, const kad_monitor_report_view* out);
+/* Host only: the validation that needs no table. */
+int kad_monitor_report_check(const kad_monitor_report_batch* batch, const kad_monitor_report_view* out);
+/* ms[0] = the zeroing, ms[1] = monitor_scan_kernel (the counters, the histograms, the timers' counts), ms[2] = the
+ * counts' exclusive sums and monitor_scatter_kernel (the timer lists). */
+int kad_monitor_report_timing(kad_ctx* ctx, float ms[3]);
+/* The launch decision (csrc/kad_monitor.h route_monitor_report): out[KAD_MON_REP_ROUTE_FIELDS] is [0] the histogram
+ * path: 0 = LDS-private (a block counts into 2 * n_types bins of its own), 1 = global atomics, [1] the bins limit: the
+ * largest n_types of the LDS-private path, [2] block threads, [3] blocks, [4] slots a lane reads per step, [5] wave
+ * tiles (the entries of the timer lists' counts). */
+#define KAD_MON_REP_ROUTE_FIELDS 6
+int kad_monitor_report_route_eval(int64_t n_slots, int32_t n_types, int32_t n_cu, int32_t* out);
+int kad_monitor_report_last_route(kad_ctx* ctx, int32_t* out);
+/* Measurement and tests only: the histogram path (0 = the route's own, 1 = LDS-private, 2 = global; LDS-private forced
+ * above the bins limit: KAD_EINVAL from that call) and the blocks (0 = the route's own) of the following reports. */
+int kad_monitor_report_debug_route(kad_ctx* ctx, int32_t force_path, int32_t force_grid);
+
 /* ------------------------------------------------ result application (§8 f3)
  * applySchedulingResult (pkg/controllers/scheduler/scheduler.go:632-695) writes a unit's result into its
  * federated object: the scheduler controller's placement (util.SetPlacementClusterNames,

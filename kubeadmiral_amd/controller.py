@@ -70,6 +70,7 @@ class BatchReconciler:
         self._clusters_key = None
         self._pass = None  # the batch the last reconcile left resident (last_pass)
         self.policy_refs = None  # policyrc.PolicyRefCounter, from the first reconcile_policy_refcounts on
+        self.meters = None  # monitor.MeterTable, from the first reconcile_monitor / monitor_report on
 
     def _framework(self, profile: Optional[dict]) -> F.Framework:
         """createFramework (scheduler.go:492, profile.go:52-82): default plugins + the profile's changes."""
@@ -643,6 +644,54 @@ class BatchReconciler:
         arrays = self.policy_refs.arrays(policies, enqueued)
         result = self.ctx.policyrc_count(**arrays) if len(arrays["pol_flags"]) else None
         return self.policy_refs.apply(result, policies)
+
+    # ------------------------------------------------------------------ monitor
+    def reconcile_monitor(self, objs: Sequence[Tuple[str, Optional[dict]]], status_objs, member_objs, now: int,
+                          status_enabled: bool = True,
+                          kind: Optional[str] = None) -> Tuple[list, List[dict]]:
+        """The monitor sub-controller for a batch of events (pkg/controllers/monitor, MonitorSubController.reconcile,
+        monitor_subcontroller.go:172-343): ``objs[i]`` is (the object's qualified name, the federated object as the
+        informer holds it now, or None), in order; ``status_objs`` / ``member_objs`` the status object and the
+        (cluster name, member object) pairs, either as dicts by qualified name (what the stores hold now) or as
+        sequences aligned with ``objs`` (what each event saw: two events of one key may differ, and the per-key
+        split runs them in order); ``now`` in ns since the Unix epoch; ``kind`` the
+        federated kind (default ``Federated<Kind>``). The meters live on this reconciler's context between calls
+        (monitor.MeterTable beside the device table). Returns (one monitor.MonitorOutcome per event, copies of the
+        objects whose ``lastGeneration`` annotation is to be written, annotated). The Update call stays with the
+        caller."""
+        from . import monitor as M
+
+        if self.meters is None:
+            self.meters = M.MeterTable()
+        kind = kind or "Federated" + self.type_config.kind
+
+        def of(src, i, name, default):
+            return src.get(name, default) if isinstance(src, dict) else src[i]
+
+        events = [dict(key=f"{kind}/{name}", obj=obj, status_enabled=status_enabled, status=of(status_objs, i, name, None),
+                       members=of(member_objs, i, name, ())) for i, (name, obj) in enumerate(objs)]
+
+        def reserve(need: int) -> None:
+            if need > self.ctx.monitor_info()["capacity"]:
+                self.ctx.monitor_reserve(max(1024, 1 << (need - 1).bit_length()))
+
+        outcomes = self.meters.reconcile(events, now, self.ctx.monitor_reconcile, reserve)
+        updates = []
+        for (_, obj), o in zip(objs, outcomes):
+            if o.update_annotation:
+                meta = dict(obj.get("metadata", {}))
+                meta["annotations"] = {**(meta.get("annotations") or {}), "lastGeneration": o.last_generation}
+                updates.append({**obj, "metadata": meta})
+        return outcomes, updates
+
+    def monitor_report(self, now: int) -> List[tuple]:
+        """DoReport (report.go:31-163) at ``now`` over every meter: one kad_monitor_report; the metrics as
+        monitor.Report.to_metrics gives them."""
+        from . import monitor as M
+
+        if self.meters is None:
+            self.meters = M.MeterTable()
+        return M.Report.from_result(self.meters, self.ctx.monitor_report(now, self.meters.n_types)).to_metrics()
 
     # ------------------------------------------------------------------ the reconcile over JSON texts
     def reconcile_texts(self, texts: Sequence, policies: Sequence, clusters: List[T.FederatedCluster],

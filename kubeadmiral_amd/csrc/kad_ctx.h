@@ -105,7 +105,18 @@ struct Stage {
   kad::GroupForce force;
 };
 enum StageId { STG_DIFF, STG_EXPLAIN, STG_OVERRIDE, STG_FOLLOWER, STG_MIGRATE, STG_TRIGGER, STG_CSTAT, STG_SAGG,
-               STG_ROLLOUT, STG_DISPATCH, STG_POLICYRC, STG_SYNCNU, STG_SYNCFIN, STG_COUNT };
+               STG_ROLLOUT, STG_DISPATCH, STG_POLICYRC, STG_SYNCNU, STG_SYNCFIN, STG_MONREC, STG_MONREP, STG_MONIO, STG_COUNT };
+
+// The monitor's meters (kad_monitor_*, DESIGN.md §7 "monitor"): the one consumer state that stays on the device
+// between calls. One slot per meter, a column per field; allocated in steps of kad_monitor.h's MON_BTILE slots and
+// zeroed, so that the report reads whole steps. live / n_slots / max_type: the host's shadow of what the calls'
+// validation needs (the slot's LIVE flag, one past the highest slot ever written, the highest type id stored).
+struct MonTable {
+  DevBuf col[5], type_id, flags;
+  int64_t cap = 0, n_slots = 0, n_live = 0;
+  int32_t max_type = -1;
+  std::vector<uint8_t> live;
+};
 
 struct kad_ctx {
   int device = 0;
@@ -157,6 +168,7 @@ struct kad_ctx {
   // the consumers of the results, one Stage each (StageId): a call's inputs and outputs in its buffer, its
   // last route and forced route beside them
   Stage stage[STG_COUNT];
+  MonTable mon;
   // override policies (kad_override_*): the resident policy-set blob, its requirement routing (the layout of
   // h_reqseg) and its rows (requirement rows [NR][nch], then M and E [R][nch] each)
   DevBuf d_ovr;

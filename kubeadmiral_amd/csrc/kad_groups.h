@@ -35,7 +35,8 @@ inline bool group_width_ok(int w, int min_width) { return w == 0 || (w >= min_wi
 // What a call's kad_*_debug_route forces on its following runs (0: the route's own). Measurement only.
 struct GroupForce {
   int32_t width = 0, long_min = 0, serial = 0;  // serial: kad_rollout_plan alone
-  int32_t path = 0;                             // kad_policyrc_count alone: 1 LDS-private, 2 global
+  int32_t path = 0;                             // kad_policyrc_count, kad_monitor_report: 1 LDS-private, 2 global
+  int32_t grid = 0;                             // kad_monitor_report alone: the scan kernel's blocks
   int long_min_or(int own) const { return long_min > 0 ? long_min : own; }
 };
 

@@ -189,6 +189,30 @@ class SyncFinView(ctypes.Structure):  # kad_sync_fin_view
                 ("reason_out", ctypes.c_void_p)]
 
 
+class MonitorBatch(ctypes.Structure):  # kad_monitor_batch
+    _fields_ = [("n_objects", ctypes.c_int32), ("n_clusters", ctypes.c_int32), ("now_ns", ctypes.c_int64),
+                ("slot", ctypes.c_void_p), ("obj_flags", ctypes.c_void_p), ("type_id", ctypes.c_void_p),
+                ("creation_ns", ctypes.c_void_p), ("sync_success_ns", ctypes.c_void_p), ("fed_off", ctypes.c_void_p),
+                ("fed_cluster", ctypes.c_void_p), ("fed_gen", ctypes.c_void_p), ("mem_off", ctypes.c_void_p),
+                ("mem_cluster", ctypes.c_void_p), ("mem_gen", ctypes.c_void_p), ("last_off", ctypes.c_void_p),
+                ("last_cluster", ctypes.c_void_p), ("last_gen", ctypes.c_void_p)]
+
+
+class MonitorView(ctypes.Structure):  # kad_monitor_view
+    _fields_ = [("result", ctypes.c_void_p), ("bits", ctypes.c_void_p), ("meter", ctypes.c_void_p),
+                ("would", ctypes.c_void_p)]
+
+
+class MonitorReportBatch(ctypes.Structure):  # kad_monitor_report_batch
+    _fields_ = [("now_ns", ctypes.c_int64), ("n_types", ctypes.c_int32), ("timer_cap", ctypes.c_int32)]
+
+
+class MonitorReportView(ctypes.Structure):  # kad_monitor_report_view
+    _fields_ = [("counters", ctypes.c_void_p), ("type_sync", ctypes.c_void_p), ("type_status", ctypes.c_void_p),
+                ("sync_slot", ctypes.c_void_p), ("sync_ms", ctypes.c_void_p), ("status_slot", ctypes.c_void_p),
+                ("status_ms", ctypes.c_void_p), ("n_timers", ctypes.c_void_p)]
+
+
 _lib = None
 
 
@@ -252,6 +276,8 @@ _CONSUMER_ABI = {
     "policyrc": ("kad_policyrc_count", (), (_I32, _I64, _I32), (_I32,)),
     "sync_needs_update": ("kad_sync_needs_update", (), (_I32, _I32), None),
     "sync_finish": ("kad_sync_finish", (), (_I32, _I32, _I64, _I32), (_I32, _I32)),
+    "monitor_reconcile": ("kad_monitor_reconcile", (), (_I32, _I32, _I64, _I32), (_I32, _I32)),
+    "monitor_report": ("kad_monitor_report", (), (_I64, _I32, _I32), (_I32, _I32)),
 }
 
 
@@ -311,6 +337,12 @@ def load_library(path: str = LIB_PATH):
         getattr(L, f"kad_{name}_last_route").argtypes = [P, P]
         if force is not None:
             getattr(L, f"kad_{name}_debug_route").argtypes = [P, *force]
+    if hasattr(L, "kad_monitor_reserve"):  # (absent from libraries of older revisions: A/B runs)
+        L.kad_monitor_reserve.argtypes = [P, _I64]
+        L.kad_monitor_load.argtypes = [P, _I32] + [P] * 8
+        L.kad_monitor_read.argtypes = [P, _I32] + [P] * 8
+        L.kad_monitor_clear.argtypes = [P]
+        L.kad_monitor_info.argtypes = [P, P]
     if hasattr(L, "kad_dispatch_decide"):
         L.kad_dispatch_decide.argtypes = [ctypes.c_uint32, ctypes.c_int32, ctypes.c_uint32, ctypes.c_uint32, P]
     L.kad_debug_inject_fault.argtypes = [P, I]
@@ -756,6 +788,59 @@ def sync_finish_check(n_clusters: int, n_reasons: int, reason_check_clusters: in
                                                   reason_ns_not_federated, **arrays))
 
 
+MONITOR_REC_ROUTE = ("width", "long_min", "threads", "grid", "long_grid", "stride")
+MONITOR_REP_ROUTE = ("path", "bins", "threads", "grid", "vec", "wtiles")
+MONITOR_PATHS = ("LDS", "GLOBAL")  # the record's path; monitor_report_debug_route forces 1 + its index
+MONITOR_COLUMNS = ("creation", "last_update", "sync_success", "last_status_synced", "out_of_sync_ns")
+MON_TIME_ZERO = -(1 << 62)
+
+
+def monitor_reconcile_route_eval(n_objects: int, n_long: int, short_items: int, n_cu: int = 256) -> dict:
+    """kad_monitor_reconcile_route_eval: the launch decision of a monitor_reconcile (needs no GPU)."""
+    return _route_eval("monitor_reconcile", MONITOR_REC_ROUTE, n_objects, n_long, short_items, n_cu, error=KadError)
+
+
+def monitor_report_route_eval(n_slots: int, n_types: int, n_cu: int = 256) -> dict:
+    """kad_monitor_report_route_eval: the launch decision of a monitor_report (needs no GPU)."""
+    return _route_eval("monitor_report", MONITOR_REP_ROUTE, n_slots, n_types, n_cu, error=KadError)
+
+
+_MONITOR_IN = (("slot", np.int32), ("obj_flags", np.uint16), ("type_id", np.int32), ("creation_ns", np.int64),
+               ("sync_success_ns", np.int64), ("fed_off", np.int32), ("fed_cluster", np.int32), ("fed_gen", np.int64),
+               ("mem_off", np.int32), ("mem_cluster", np.int32), ("mem_gen", np.int64), ("last_off", np.int32),
+               ("last_cluster", np.int32), ("last_gen", np.int64))
+_MONITOR_OUT = (("result", np.uint8, 0), ("bits", np.uint8, 0), ("meter", np.int64, 1), ("would", np.int64, 2))
+_MONITOR_REP_OUT = (("counters", np.int32, 0), ("type_sync", np.int32, 1), ("type_status", np.int32, 1),
+                    ("sync_slot", np.int32, 2), ("sync_ms", np.int64, 2), ("status_slot", np.int32, 2),
+                    ("status_ms", np.int64, 2), ("n_timers", np.int32, 3))
+
+
+def monitor_reconcile_args(n_clusters: int, now_ns: int, **arrays):
+    """The kad_monitor_batch / kad_monitor_view of one call with the arrays that back them (the batch's fields by
+    name; n_objects is taken from obj_flags as it is, so that a malformed batch reaches the library's validation).
+    Returns (batch, view, the input arrays, the output arrays by name)."""
+    a = _flat(_MONITOR_IN, arrays)
+    O = len(a["obj_flags"]) if "obj_flags" in a else 0
+    return _call_args(MonitorBatch, MonitorView, (O, int(n_clusters), int(now_ns)), _MONITOR_IN, _MONITOR_OUT, a,
+                      {0: O, 1: 5 * O, 2: 2 * O})
+
+
+def monitor_reconcile_check(n_clusters: int, now_ns: int, **arrays) -> int:
+    """kad_monitor_reconcile_check: the call's validation that needs no table; no GPU."""
+    return _check("monitor_reconcile", monitor_reconcile_args(n_clusters, now_ns, **arrays))
+
+
+def monitor_report_args(now_ns: int, n_types: int, timer_cap: int):
+    """The kad_monitor_report_batch / kad_monitor_report_view of one call and its output arrays by name."""
+    return _call_args(MonitorReportBatch, MonitorReportView, (int(now_ns), int(n_types), int(timer_cap)), (),
+                      _MONITOR_REP_OUT, {}, {0: 14, 1: max(0, int(n_types)), 2: max(0, int(timer_cap)), 3: 2})
+
+
+def monitor_report_check(now_ns: int, n_types: int, timer_cap: int) -> int:
+    """kad_monitor_report_check: the call's validation that needs no table; no GPU."""
+    return _check("monitor_report", monitor_report_args(now_ns, n_types, timer_cap))
+
+
 class Context:
     """A kad_ctx: one HIP device, one stream, resident snapshot + batch."""
 
@@ -1186,6 +1271,105 @@ class Context:
         """kad_sync_finish_debug_route: the lane-group width and long_min of the following sync_finish() calls (0:
         the route's own). Measurement and tests only."""
         self._debug_route("sync_finish", width, long_min)
+
+    # ---- the monitor's resident meter table (kad_monitor_*)
+    def monitor_reserve(self, capacity: int) -> None:
+        """kad_monitor_reserve: the meter table holds at least ``capacity`` slots; its contents stay."""
+        self._chk(self.L.kad_monitor_reserve(self.h, int(capacity)))
+
+    def monitor_info(self) -> dict:
+        """kad_monitor_info: the table's capacity, n_slots (what a report walks), live slots and highest type id."""
+        out = (ctypes.c_int64 * 4)()
+        self._chk(self.L.kad_monitor_info(self.h, out))
+        return dict(zip(("capacity", "n_slots", "n_live", "max_type"), (int(x) for x in out)))
+
+    def monitor_load(self, slots, type_id=None, flags=None, **columns) -> None:
+        """kad_monitor_load: writes the listed slots' given columns (MONITOR_COLUMNS by name, int64 ns), type ids
+        and flags (KAD_MON_LIVE); a column left out keeps its contents."""
+        sl = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        bad = set(columns) - set(MONITOR_COLUMNS)
+        if bad:
+            raise TypeError(f"unknown monitor columns {sorted(bad)}")
+        cols = [None if k not in columns else np.ascontiguousarray(columns[k], np.int64).reshape(-1) for k in MONITOR_COLUMNS]
+        ty = None if type_id is None else np.ascontiguousarray(type_id, np.int32).reshape(-1)
+        fl = None if flags is None else np.ascontiguousarray(flags, np.uint8).reshape(-1)
+        for a in cols + [ty, fl]:
+            if a is not None and len(a) != len(sl):
+                raise ValueError("monitor_load: a column's length differs from the slots'")
+        self._chk(self.L.kad_monitor_load(self.h, len(sl), _p(sl), *(_p(a) for a in cols), _p(ty), _p(fl)))
+
+    def monitor_read(self, slots) -> dict:
+        """kad_monitor_read → the listed slots' MONITOR_COLUMNS, ``type_id`` and ``flags``."""
+        sl = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        n = max(1, len(sl))
+        out = {k: np.zeros(n, np.int64) for k in MONITOR_COLUMNS}
+        out["type_id"] = np.zeros(n, np.int32)
+        out["flags"] = np.zeros(n, np.uint8)
+        self._chk(self.L.kad_monitor_read(self.h, len(sl), _p(sl), *(_p(a) for a in out.values())))
+        return {k: v[:len(sl)] for k, v in out.items()}
+
+    def monitor_clear(self) -> None:
+        """kad_monitor_clear: no slot is live; the capacity stays."""
+        self._chk(self.L.kad_monitor_clear(self.h))
+
+    def monitor_reconcile(self, n_clusters: int, now_ns: int, **arrays) -> dict:
+        """kad_monitor_reconcile → {result[O], bits[O], meter[O, 5], would[O, 2]}. Arguments as
+        :func:`monitor_reconcile_args` (monitor.MonitorBatch.arrays())."""
+        out = self._consume("kad_monitor_reconcile", monitor_reconcile_args(n_clusters, now_ns, **arrays))
+        out["meter"] = out["meter"].reshape(-1, 5)
+        out["would"] = out["would"].reshape(-1, 2)
+        return out
+
+    def monitor_report(self, now_ns: int, n_types: int, timer_cap: Optional[int] = None) -> dict:
+        """kad_monitor_report → {counters[14], type_sync[n_types], type_status[n_types], sync_slot / sync_ms and
+        status_slot / status_ms cut to their lengths, n_timers[2]}. ``timer_cap`` defaults to the longer list of
+        this context's last report plus a quarter (1024 at least), so that a steady table is walked once; a list
+        that is longer all the same is fetched again with room for it."""
+        if timer_cap is None:
+            timer_cap = max(1024, getattr(self, "_monitor_timer_cap", 0))
+        while True:
+            args = monitor_report_args(now_ns, n_types, timer_cap)
+            b, v, _, out = args
+            rc = self.L.kad_monitor_report(self.h, ctypes.byref(b), ctypes.byref(v))
+            need = int(out["n_timers"].max())
+            if rc == KAD_ENOSPC and need > timer_cap:
+                timer_cap = need
+                continue
+            self._chk(rc)
+            self._monitor_timer_cap = need + need // 4
+            ns, nt = (int(x) for x in out["n_timers"])
+            for k in ("sync_slot", "sync_ms"):
+                out[k] = out[k][:ns]
+            for k in ("status_slot", "status_ms"):
+                out[k] = out[k][:nt]
+            return out
+
+    def monitor_reconcile_timing(self):
+        """kad_monitor_reconcile_timing: ms of the last monitor_reconcile() (inputs in, the kernel, outputs back)."""
+        return self._timing("monitor_reconcile", 3)
+
+    def monitor_report_timing(self):
+        """kad_monitor_report_timing: ms of the last monitor_report() (the zeroing, monitor_scan_kernel, the
+        offsets and monitor_scatter_kernel)."""
+        return self._timing("monitor_report", 3)
+
+    def monitor_reconcile_last_route(self) -> dict:
+        """kad_monitor_reconcile_last_route: what the last monitor_reconcile() launched."""
+        return self._last_route("monitor_reconcile", MONITOR_REC_ROUTE)
+
+    def monitor_report_last_route(self) -> dict:
+        """kad_monitor_report_last_route: what the last monitor_report() launched."""
+        return self._last_route("monitor_report", MONITOR_REP_ROUTE)
+
+    def monitor_reconcile_debug_route(self, width: int = 0, long_min: int = 0) -> None:
+        """kad_monitor_reconcile_debug_route: the lane-group width and long_min of the following calls (0: the
+        route's own)."""
+        self._debug_route("monitor_reconcile", width, long_min)
+
+    def monitor_report_debug_route(self, path: int = 0, grid: int = 0) -> None:
+        """kad_monitor_report_debug_route: the histogram path (1 LDS-private, 2 global) and the blocks of the
+        following reports (0: the route's own)."""
+        self._debug_route("monitor_report", path, grid)
 
     def policyrc_debug_route(self, path: int = 0) -> None:
         """kad_policyrc_debug_route: the count kernel's path of the following policyrc_count() calls (0: the

@@ -1625,3 +1625,79 @@ def gen_sync_finish(seed: int, W: int, C: int, touched: int, steady: float = 0.8
             "ver_flags": np.array([0] + [3] * 8 + [1], np.uint8),
             "ver_off": np.concatenate(([0], np.cumsum(ne + nv))).astype(np.int64),
             "st_off": np.concatenate(([0], np.cumsum(ne))).astype(np.int64)}
+
+
+def gen_monitor_events(seed: int, n_objects: int = 40, n_clusters: int = 6, rounds: int = 4, kinds=("FederatedDeployment", "FederatedJob"),
+                       t0_ns: int = 1_700_000_000_000_000_000, max_list: Optional[int] = None):
+    """Seeded monitor events (monitor.py's event dicts): ``rounds`` lists of (now_ns, events) over a pool of
+    ``n_objects`` keys of ``kinds``. Every branch of MonitorSubController.reconcile turns up: absent and deleted
+    objects, missing / unparsable / fractional syncSuccessTimestamp, lastGeneration and lastSyncSuccessGeneration
+    equal, different or zero-padded, status absent, clusterStatus entries without a name or a generation, member
+    objects without one, member lists equal to the fed list, to the previous one, or neither; keys repeat within a
+    round."""
+    import random
+    from datetime import datetime, timezone
+
+    rng = random.Random(seed)
+    max_list = n_clusters if max_list is None else max_list
+
+    def stamp(ns: int) -> str:
+        s, f = divmod(ns, 10 ** 9)
+        base = datetime.fromtimestamp(s, timezone.utc).strftime("%Y-%m-%dT%H:%M:%S")
+        return base + (("." + ("%09d" % f).rstrip("0")) if f else "") + "Z"
+
+    keys = [f"{rng.choice(kinds)}/ns{j % 3}/obj{j}" for j in range(n_objects)]
+    gens = {k: rng.randrange(1, 9) for k in keys}
+    prev: dict = {}
+    out = []
+    now = t0_ns
+    for _ in range(rounds):
+        now += rng.randrange(1, 40 * 60) * 10 ** 9 + rng.randrange(10 ** 9)
+        events = []
+        for _ in range(rng.randrange(n_objects // 2, 2 * n_objects)):
+            k = rng.choice(keys)
+            r = rng.random()
+            if r < 0.06:
+                events.append(dict(key=k, obj=None, status_enabled=True, status=None, members=[]))
+                continue
+            if rng.random() < 0.3:
+                gens[k] += 1
+            g = gens[k]
+            ann = {}
+            r = rng.random()
+            if r < 0.6:
+                ann["syncSuccessTimestamp"] = stamp(now - rng.randrange(0, 3 * 3600 * 10 ** 9))
+            elif r < 0.7:
+                ann["syncSuccessTimestamp"] = rng.choice(["yesterday", "2023-13-01T00:00:00Z", ""])
+            r = rng.random()
+            if r < 0.8:
+                ann["lastGeneration"] = rng.choice([str(g), str(g), str(g - 1), "0%d" % g])
+            if rng.random() < 0.7:
+                ann["lastSyncSuccessGeneration"] = rng.choice([str(g), str(g), str(g - 1)])
+            meta = dict(generation=g, annotations=ann)
+            if rng.random() < 0.9:
+                meta["creationTimestamp"] = stamp(t0_ns - rng.randrange(0, 10 * 86400) * 10 ** 9)
+            if rng.random() < 0.04:
+                meta["deletionTimestamp"] = stamp(now)
+            ids = sorted(rng.sample(range(n_clusters), rng.randrange(0, max_list + 1)))
+            fed = {f"c{c}": rng.randrange(1, 4) for c in ids}
+            r = rng.random()
+            mem = dict(fed) if r < 0.45 else dict(prev.get(k, fed)) if r < 0.7 else \
+                {c: v + (rng.random() < 0.3) for c, v in fed.items()}
+            prev[k] = mem
+            cs = [dict(clusterName=c, status=dict(observedGeneration=v)) for c, v in fed.items()]
+            r = rng.random()
+            if cs and r < 0.04:
+                del cs[rng.randrange(len(cs))]["clusterName"]
+            elif cs and r < 0.08:
+                cs[rng.randrange(len(cs))]["status"] = {}
+            elif cs and r < 0.12:
+                cs.append(dict(cs[0], status=dict(observedGeneration=cs[0]["status"].get("observedGeneration", 1) + 1)))
+            members = [(c, dict(status=dict(observedGeneration=v))) for c, v in mem.items()]
+            if members and rng.random() < 0.04:
+                members[rng.randrange(len(members))] = (members[0][0], dict(status={}))
+            status = None if rng.random() < 0.05 else dict(metadata={}, clusterStatus=cs)
+            events.append(dict(key=k, obj=dict(metadata=meta), status_enabled=rng.random() < 0.9, status=status,
+                               members=members))
+        out.append((now, events))
+    return out
