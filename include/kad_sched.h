@@ -1599,6 +1599,118 @@ int kad_monitor_report_last_route(kad_ctx* ctx, int32_t* out);
  * above the bins limit: KAD_EINVAL from that call) and the blocks (0 = the route's own) of the following reports. */
 int kad_monitor_report_debug_route(kad_ctx* ctx, int32_t force_path, int32_t force_grid);
 
+/* ------------------------------------------------------ revision history: current, numbered and truncated revisions
+ * The sync controller's syncRevisions (pkg/controllers/sync/history.go:36-120, with pkg/controllers/util/history/
+ * controller_history.go:91-176) for a batch of federated objects of a type with revisionHistoryEnabled, between
+ * ensureFinalizer and ensureAnnotations (sync/controller.go:401-409). The API calls are never made: the product is, per
+ * object, the ordered plan of actions on its listed ControllerRevisions and what the three return values are built from.
+ *
+ * Inputs. One blob holds every object's patch (getPatch, history.go:252-278: the caller's json.Marshal) and every
+ * listed revision's Data.Raw, each at a multiple of 16 bytes and followed by the bytes up to the next multiple of 16
+ * (any value: they are not compared or hashed, only read). Per object: limit = spec.revisionHistoryLimit (0: the
+ * object gets no actions, hash 0 and nothing of it is read, history.go:47-50; the caller also passes 0 for an object
+ * whose patch failed); collision = the collision count, hashed only with KAD_REV_OBJ_COLLISION (a non-nil pointer);
+ * patch_off / patch_len; rev_off[O + 1]: its listed revisions in list order (ListControllerRevisions' filter is the
+ * caller's), at most KAD_REV_MAX_REVISIONS each (more: KAD_EUNSUPPORTED); want_off[O + 1] / want_lab: the wanted labels
+ * (uid plus the object's labels, history.go:291-304) as ids of (key, value) pairs interned per batch, strictly
+ * ascending. Per revision: rev_data_off / rev_data_len; rev_revision; rev_time = creationTimestamp in seconds;
+ * rev_name_rank = the rank of its name among its object's revisions' names in byte order, equal names equal ranks;
+ * rev_flags: KAD_REV_HASH_PARSED = strconv.ParseInt(its controller.kubernetes.io/hash label, 10, 32) succeeds, rev_hash
+ * = uint32 of that number; rev_lab_off[R + 1] / rev_lab: its labels as pair ids, strictly ascending.
+ *
+ * Per object with limit != 0: (1) hash = FNV-1 32 (fnv.New32) over the patch, then with KAD_REV_OBJ_COLLISION over the
+ * ASCII of strconv.FormatInt(collision, 10) (controller_history.go:93-105). (2) The update revision's own hash label
+ * is rand.SafeEncodeString(fmt.Sprint(hash)): upd_parsed = ParseInt accepts it (the decimal holds no digit above 5 and,
+ * every digit raised by 4, is at most 2^31 - 1), upd_hash its uint32. (3) equal[r] = EqualRevision(listed, update)
+ * (:120-143): the lengths equal, not both labels parsed with different numbers, the bytes equal. (4) The equal ones
+ * are current, the others old; rev_number = max(0, max old Revision) + 1 in wrapping int64 (history.go:71). (5) No
+ * current one: KAD_REV_ACT_CREATE (revision index -1). Else keep = the first current one with the largest Revision
+ * (:221-228); KAD_REV_ACT_DELETE for every other current one whose name differs from the kept one's, in list order;
+ * then KAD_REV_ACT_RENUMBER(keep) if its Revision < rev_number, else KAD_REV_ACT_RELABEL(keep) unless its labels hold
+ * every wanted pair (:83-93, 122-162). (6) order = the old ones in sort.Stable(byRevision) order (Revision, rev_time,
+ * name, then list index); the first min(n_old, max(0, n_old - limit)) of them (Go's wrapping int) get DELETE
+ * (:164-183). (7) last = the last of order if n_old >= 1 and limit >= 1, else -1 (:103-105). (8) Every old one in
+ * sorted order, the deleted ones included, gets RELABEL unless its labels hold every wanted pair (:114-118).
+ * IsLabelSubset reads a missing key as "": an object whose wanted set holds an empty value is marked
+ * KAD_REV_OBJ_LABELS_ON_HOST, the device emits no RELABEL for it and the caller decides them from keep, order and
+ * rev_number. Actions go to act_kind / act_rev (a revision's index within its object) from out_off[o], n_actions[o] of
+ * them; out_off[O + 1] is computed by the call (2 n + 1 slots for an object of n revisions) and returned in the view;
+ * action_capacity = what act_kind / act_rev hold (less than out_off[O]: KAD_ENOSPC). Slots behind an object's counts,
+ * and order / equal of an object with limit 0, are unspecified.
+ *
+ * Everything is validated on the host before anything is launched (KAD_EINVAL): counts, offsets, data outside the
+ * blob or not 16-byte aligned, unknown flag bits, name ranks outside the object, pair lists not strictly ascending or
+ * outside [0, n_pairs), missing arrays. Three kernels on the ctx stream (hr_hash_kernel, hr_compare_kernel,
+ * hr_plan_kernel: kad_history.hip); the call blocks until the outputs are in the caller's buffers. Integers only, no
+ * atomics. It needs no snapshot and reads no resident state, so a kad_group member accepts it. n_objects == 0 returns
+ * 0 without launching. */
+#define KAD_REV_MAX_REVISIONS 4096
+#define KAD_REV_OBJ_COLLISION 1u
+#define KAD_REV_OBJ_LABELS_ON_HOST 2u
+#define KAD_REV_HASH_PARSED 1u
+#define KAD_REV_ACT_CREATE 1u
+#define KAD_REV_ACT_DELETE 2u
+#define KAD_REV_ACT_RENUMBER 3u
+#define KAD_REV_ACT_RELABEL 4u
+typedef struct kad_revision_batch {
+  int32_t n_objects; /* O */
+  int32_t n_pairs;   /* interned (key, value) label pairs */
+  int64_t blob_len;
+  int64_t action_capacity;
+  const int64_t* limit;         /* [O] */
+  const int32_t* collision;     /* [O] */
+  const uint8_t* obj_flags;     /* [O] KAD_REV_OBJ_* */
+  const int64_t* patch_off;     /* [O] multiples of 16 */
+  const int32_t* patch_len;     /* [O] */
+  const uint8_t* blob;          /* [blob_len] */
+  const int32_t* rev_off;       /* [O + 1] */
+  const int64_t* rev_data_off;  /* [R] multiples of 16 */
+  const int32_t* rev_data_len;  /* [R] */
+  const int64_t* rev_revision;  /* [R] */
+  const int64_t* rev_time;      /* [R] */
+  const int32_t* rev_name_rank; /* [R] */
+  const uint8_t* rev_flags;     /* [R] KAD_REV_HASH_PARSED */
+  const uint32_t* rev_hash;     /* [R] */
+  const int32_t* rev_lab_off;   /* [R + 1] */
+  const int32_t* rev_lab;
+  const int32_t* want_off;      /* [O + 1] */
+  const int32_t* want_lab;
+} kad_revision_batch;
+typedef struct kad_revision_view {
+  int64_t* out_off;     /* [O + 1] written by the call */
+  uint32_t* hash;       /* [O] */
+  uint32_t* upd_hash;   /* [O] */
+  uint8_t* upd_parsed;  /* [O] */
+  uint8_t* equal;       /* [R] */
+  int32_t* order;       /* [R] object o's sorted old revisions at rev_off[o] .. + n_old[o] */
+  int32_t* n_old;       /* [O] */
+  int32_t* keep;        /* [O] -1: no current revision */
+  int32_t* n_actions;   /* [O] */
+  int32_t* last;        /* [O] */
+  int64_t* rev_number;  /* [O] */
+  uint8_t* act_kind;    /* [action_capacity] KAD_REV_ACT_* */
+  int32_t* act_rev;     /* [action_capacity] */
+} kad_revision_view;
+int kad_revision_plan(kad_ctx* ctx, const kad_revision_batch* batch, const kad_revision_view* out);
+/* Host only (no device, no ctx): the same validation. */
+int kad_revision_plan_check(const kad_revision_batch* batch, const kad_revision_view* out);
+/* ms[0] = hr_hash_kernel, ms[1] = hr_compare_kernel, ms[2] = hr_plan_kernel (the copies either side are not in them). */
+int kad_revision_plan_timing(kad_ctx* ctx, float ms[3]);
+/* csrc/kad_history.h route_revision: n_hash = the objects with limit != 0, n_long = the objects with more revisions
+ * than the route's long_min, short_revs = the other objects' revisions, n_pairs = all revisions, pair_chunks = their data
+ * lengths in 16-byte chunks (rounded up each). out[KAD_REV_ROUTE_FIELDS] is [0] the plan kernel's lanes per object
+ * (the mean revisions of a short object, a power of two in [1, 64]), [1] long_min, [2] the compare kernel's lanes per
+ * pair (the mean chunks of a pair over the chunks a lane takes), [3] hash-kernel blocks (a lane per object, in
+ * descending order of patch length), [4] compare-kernel blocks, [5] plan-kernel blocks of the group path, [6] of the long
+ * path (one object per block), [7] block threads. */
+#define KAD_REV_ROUTE_FIELDS 8
+int kad_revision_plan_route_eval(int32_t n_objects, int32_t n_hash, int32_t n_long, int64_t short_revs, int64_t n_pairs,
+                                 int64_t pair_chunks, int32_t n_cu, int32_t* out);
+int kad_revision_plan_last_route(kad_ctx* ctx, int32_t* out);
+/* Measurement and tests only: the lane-group width of the compare and the plan kernel (0, or a power of two in
+ * [1, 64]) and long_min (0: the route's own) of the following kad_revision_plan calls. */
+int kad_revision_plan_debug_route(kad_ctx* ctx, int32_t force_width, int32_t force_long_min);
+
 /* ------------------------------------------------ result application (§8 f3)
  * applySchedulingResult (pkg/controllers/scheduler/scheduler.go:632-695) writes a unit's result into its
  * federated object: the scheduler controller's placement (util.SetPlacementClusterNames,

@@ -623,6 +623,28 @@ class BatchReconciler:
                 fed["status"] = o.status
         return out
 
+    # ------------------------------------------------------------------ revision history
+    def reconcile_revisions(self, objs: Sequence[dict], revisions: Sequence[Sequence[dict]],
+                            pod_template_hashes: Optional[Sequence[Optional[str]]] = None) -> list:
+        """The sync controller's syncRevisions for a batch of federated objects (pkg/controllers/sync/history.go:36-120,
+        called at sync/controller.go:401-409 for a type with revisionHistoryEnabled): ``revisions[i]`` are the
+        ControllerRevisions listed for ``objs[i]`` (history.list_revisions over the informer's store), in list order;
+        ``pod_template_hashes[i]`` the object's getPodTemplateHash, appended to lastRevisionNameWithHash behind a ``|``
+        where given (its go-spew hashing is the caller's). One kad_revision_plan hashes every patch, compares it with
+        every listed revision's data and plans the creates, deletes, renumbers and relabels (history.RevisionBatch).
+        Returns per object a history.RevisionOutcome: the ordered actions and syncRevisions' three return values, of
+        which ``current_revision_name`` and ``last_revision_name_with_hash`` are what ensureAnnotations writes; a type
+        without revisionHistoryEnabled gets empty outcomes. The API calls, the create-collision retry and the
+        annotations' write stay with the caller."""
+        from . import history as H
+
+        if not self.type_config.revision_history:
+            return [H.RevisionOutcome() for _ in objs]
+        batch = H.batch_of(objs, revisions, pod_template_hashes)
+        if not len(batch):
+            return []
+        return batch.apply(self.ctx.revision_plan(**batch.arrays()))
+
     # ------------------------------------------------------------------ policy reference counts
     def reconcile_policy_refcounts(self, events: Sequence[Tuple[object, Optional[dict]]], policies: Dict[tuple, dict],
                                    enqueued: Sequence[tuple] = ()) -> Tuple[list, list]:

@@ -24,11 +24,10 @@
 // Work: 256·|cluster part| FNV steps per pass + each object's own bytes,
 // instead of |cluster part| per object.
 #include "kad_device.h"
+#include "kad_fnv.h"
 
 namespace kad {
 
-constexpr uint32_t kFnvPrime = 16777619u;
-constexpr uint32_t kFnvOffset = 2166136261u;
 constexpr int kComposeGroup = 32;  // tables composed per workgroup (32 KiB of LDS)
 
 __host__ __device__ inline uint32_t fnv_pow(uint64_t n) {
@@ -39,13 +38,6 @@ __host__ __device__ inline uint32_t fnv_pow(uint64_t n) {
     n >>= 1;
   }
   return r;
-}
-
-__device__ __forceinline__ uint32_t fnv_word(uint32_t h, uint32_t w) {
-  h = (h * kFnvPrime) ^ (w & 0xffu);
-  h = (h * kFnvPrime) ^ ((w >> 8) & 0xffu);
-  h = (h * kFnvPrime) ^ ((w >> 16) & 0xffu);
-  return (h * kFnvPrime) ^ (w >> 24);
 }
 
 // grid = n_seg workgroups of 256 lanes (lane = residue). seg_len is a multiple of 64.

@@ -322,6 +322,65 @@ def marshal(v) -> bytes:
     return "".join(out).encode("utf-8")
 
 
+def _go_float(f: float) -> str:
+    """encoding/json's floatEncoder for a float64: strconv's shortest digits, 'e' below 1e-6 and from 1e21 on with
+    the exponent's leading zero dropped, else 'f'."""
+    from decimal import Decimal
+
+    if f != f or f in (float("inf"), float("-inf")):
+        raise TypeError("json: unsupported value")
+    if f == 0:
+        return "-0" if str(f).startswith("-") else "0"
+    d = Decimal(repr(f)).normalize()
+    a = abs(f)
+    if a < 1e-6 or a >= 1e21:
+        sign, digits, exp = d.as_tuple()
+        e = exp + len(digits) - 1
+        mant = str(digits[0]) + ("." + "".join(map(str, digits[1:])) if len(digits) > 1 else "")
+        es = f"{abs(e):02d}"
+        if e < 0 and es[0] == "0" and len(es) == 2:
+            es = es[1]  # e-09 is written e-9 (and e+21 stays)
+        return ("-" if sign else "") + mant + "e" + ("-" if e < 0 else "+") + es
+    return format(d, "f")
+
+
+def _enc_unstructured(v, out: List[str]) -> None:
+    if isinstance(v, dict):
+        out.append("{")
+        for i, k in enumerate(sorted(v, key=lambda k: k.encode("utf-8", "surrogatepass"))):
+            if i:
+                out.append(",")
+            _enc_str(k, out)
+            out.append(":")
+            _enc_unstructured(v[k], out)
+        out.append("}")
+    elif isinstance(v, (list, tuple)):
+        out.append("[")
+        for i, x in enumerate(v):
+            if i:
+                out.append(",")
+            _enc_unstructured(x, out)
+        out.append("]")
+    elif isinstance(v, float):
+        out.append(_go_float(v))
+    else:
+        _enc(v, out)
+
+
+def marshal_unstructured(v) -> bytes:
+    """json.Marshal of an unstructured value (map[string]interface{} / []interface{} / string / bool / int64 /
+    float64 / nil): map keys in byte order, floats as encoding/json writes a float64."""
+    out: List[str] = []
+    _enc_unstructured(v, out)
+    return "".join(out).encode("utf-8")
+
+
+def revision_patch(template) -> bytes:
+    """getPatch's bytes (pkg/controllers/sync/history.go:273-277) for the object's spec.template.spec.template:
+    json.Marshal([]interface{}{{"op": "replace", "path": "/spec/template/spec/template", "value": template}})."""
+    return marshal_unstructured([{"op": "replace", "path": "/spec/template/spec/template", "value": template}])
+
+
 def atoi(s: str) -> Optional[int]:
     """strconv.Atoi on a 64-bit platform; None where Go returns an error."""
     body = s[1:] if s[:1] in ("+", "-") else s

@@ -195,6 +195,7 @@ class FederatedTypeConfig:
     ready_replicas_status: str = ""  # Spec.PathDefinition.ReadyReplicasStatus (auto migration: ready replicas)
     available_replicas_status: str = ""  # Spec.PathDefinition.AvailableReplicasStatus (rollout planning)
     rollout_plan: bool = False       # Spec.RolloutPlan == Enabled (extensions_federatedtypeconfig.go:90-92)
+    revision_history: bool = False   # Spec.RevisionHistory == Enabled (GetRevisionHistoryEnabled)
 
     @property
     def namespaced(self) -> bool:

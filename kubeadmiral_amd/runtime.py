@@ -203,6 +203,25 @@ class MonitorView(ctypes.Structure):  # kad_monitor_view
                 ("would", ctypes.c_void_p)]
 
 
+class RevisionBatch(ctypes.Structure):  # kad_revision_batch
+    _fields_ = [("n_objects", ctypes.c_int32), ("n_pairs", ctypes.c_int32), ("blob_len", ctypes.c_int64),
+                ("action_capacity", ctypes.c_int64), ("limit", ctypes.c_void_p), ("collision", ctypes.c_void_p),
+                ("obj_flags", ctypes.c_void_p), ("patch_off", ctypes.c_void_p), ("patch_len", ctypes.c_void_p),
+                ("blob", ctypes.c_void_p), ("rev_off", ctypes.c_void_p), ("rev_data_off", ctypes.c_void_p),
+                ("rev_data_len", ctypes.c_void_p), ("rev_revision", ctypes.c_void_p), ("rev_time", ctypes.c_void_p),
+                ("rev_name_rank", ctypes.c_void_p), ("rev_flags", ctypes.c_void_p), ("rev_hash", ctypes.c_void_p),
+                ("rev_lab_off", ctypes.c_void_p), ("rev_lab", ctypes.c_void_p), ("want_off", ctypes.c_void_p),
+                ("want_lab", ctypes.c_void_p)]
+
+
+class RevisionView(ctypes.Structure):  # kad_revision_view
+    _fields_ = [("out_off", ctypes.c_void_p), ("hash", ctypes.c_void_p), ("upd_hash", ctypes.c_void_p),
+                ("upd_parsed", ctypes.c_void_p), ("equal", ctypes.c_void_p), ("order", ctypes.c_void_p),
+                ("n_old", ctypes.c_void_p), ("keep", ctypes.c_void_p), ("n_actions", ctypes.c_void_p),
+                ("last", ctypes.c_void_p), ("rev_number", ctypes.c_void_p), ("act_kind", ctypes.c_void_p),
+                ("act_rev", ctypes.c_void_p)]
+
+
 class MonitorReportBatch(ctypes.Structure):  # kad_monitor_report_batch
     _fields_ = [("now_ns", ctypes.c_int64), ("n_types", ctypes.c_int32), ("timer_cap", ctypes.c_int32)]
 
@@ -278,6 +297,7 @@ _CONSUMER_ABI = {
     "sync_finish": ("kad_sync_finish", (), (_I32, _I32, _I64, _I32), (_I32, _I32)),
     "monitor_reconcile": ("kad_monitor_reconcile", (), (_I32, _I32, _I64, _I32), (_I32, _I32)),
     "monitor_report": ("kad_monitor_report", (), (_I64, _I32, _I32), (_I32, _I32)),
+    "revision_plan": ("kad_revision_plan", (), (_I32, _I32, _I32, _I64, _I64, _I64, _I32), (_I32, _I32)),
 }
 
 
@@ -841,6 +861,47 @@ def monitor_report_check(now_ns: int, n_types: int, timer_cap: int) -> int:
     return _check("monitor_report", monitor_report_args(now_ns, n_types, timer_cap))
 
 
+REVISION_ROUTE = ("width", "long_min", "cmp_width", "hash_grid", "cmp_grid", "grid", "long_grid", "threads")
+
+
+def revision_plan_route_eval(n_objects: int, n_hash: int, n_long: int, short_revs: int, n_pairs: int, pair_chunks: int,
+                             n_cu: int = 256) -> dict:
+    """kad_revision_plan_route_eval: the launch decision of a revision_plan (needs no GPU)."""
+    return _route_eval("revision_plan", REVISION_ROUTE, n_objects, n_hash, n_long, short_revs, n_pairs, pair_chunks, n_cu,
+                       error=KadError)
+
+
+_REVISION_IN = (("limit", np.int64), ("collision", np.int32), ("obj_flags", np.uint8), ("patch_off", np.int64),
+                ("patch_len", np.int32), ("blob", np.uint8), ("rev_off", np.int32), ("rev_data_off", np.int64),
+                ("rev_data_len", np.int32), ("rev_revision", np.int64), ("rev_time", np.int64), ("rev_name_rank", np.int32),
+                ("rev_flags", np.uint8), ("rev_hash", np.uint32), ("rev_lab_off", np.int32), ("rev_lab", np.int32),
+                ("want_off", np.int32), ("want_lab", np.int32))
+_REVISION_OUT = (("out_off", np.int64, 3), ("hash", np.uint32, 0), ("upd_hash", np.uint32, 0), ("upd_parsed", np.uint8, 0),
+                 ("equal", np.uint8, 1), ("order", np.int32, 1), ("n_old", np.int32, 0), ("keep", np.int32, 0),
+                 ("n_actions", np.int32, 0), ("last", np.int32, 0), ("rev_number", np.int64, 0), ("act_kind", np.uint8, 2),
+                 ("act_rev", np.int32, 2))
+
+
+def revision_plan_args(n_pairs: int, **arrays):
+    """The kad_revision_batch / kad_revision_view of one call with the arrays that back them (the batch's fields by
+    name; n_objects is taken from obj_flags and blob_len from blob as they are, so that a malformed batch reaches the
+    library's validation; ``n_objects``, ``blob_len`` and ``action_capacity`` override them, the last defaulting to
+    2 R + O). Returns (batch, view, the input arrays, the output arrays by name)."""
+    a = _flat(_REVISION_IN, arrays)
+    n = lambda k: len(a[k]) if k in a else 0  # noqa: E731
+    O = int(arrays.get("n_objects", n("obj_flags")))
+    R = n("rev_flags")
+    cap = int(arrays.get("action_capacity", 2 * R + max(O, 0)))
+    counts = (O, int(n_pairs), int(arrays.get("blob_len", n("blob"))), cap)
+    return _call_args(RevisionBatch, RevisionView, counts, _REVISION_IN, _REVISION_OUT, a,
+                      {0: max(O, 0), 1: R, 2: max(cap, 0), 3: max(O, 0) + 1})
+
+
+def revision_plan_check(n_pairs: int, **arrays) -> int:
+    """kad_revision_plan_check: kad_revision_plan's validation of :func:`revision_plan_args` arguments; no GPU."""
+    return _check("revision_plan", revision_plan_args(n_pairs, **arrays))
+
+
 class Context:
     """A kad_ctx: one HIP device, one stream, resident snapshot + batch."""
 
@@ -1266,6 +1327,27 @@ class Context:
     def sync_finish_last_route(self) -> dict:
         """kad_sync_finish_last_route: what the last sync_finish() launched (sync_finish_route_eval's record)."""
         return self._last_route("sync_finish", SYNC_FIN_ROUTE)
+
+    def revision_plan(self, n_pairs: int, **arrays) -> dict:
+        """kad_revision_plan → {out_off[O + 1], hash[O], upd_hash[O], upd_parsed[O], equal[R], order[R] (object o's
+        sorted old revisions at rev_off[o] .. + n_old[o]), n_old[O], keep[O], n_actions[O], last[O], rev_number[O],
+        act_kind / act_rev (object o's actions at out_off[o] .. + n_actions[o])}. Arguments as
+        :func:`revision_plan_args` (history.RevisionBatch.arrays())."""
+        return self._consume("kad_revision_plan", revision_plan_args(n_pairs, **arrays))
+
+    def revision_plan_timing(self):
+        """kad_revision_plan_timing: ms of the last revision_plan() — (hr_hash_kernel, hr_compare_kernel,
+        hr_plan_kernel)."""
+        return self._timing("revision_plan", 3)
+
+    def revision_plan_last_route(self) -> dict:
+        """kad_revision_plan_last_route: what the last revision_plan() launched (revision_plan_route_eval's record)."""
+        return self._last_route("revision_plan", REVISION_ROUTE)
+
+    def revision_plan_debug_route(self, width: int = 0, long_min: int = 0) -> None:
+        """kad_revision_plan_debug_route: the lane-group width of the compare and the plan kernel and long_min of the
+        following revision_plan() calls (0: the route's own)."""
+        self._debug_route("revision_plan", width, long_min)
 
     def sync_finish_debug_route(self, width: int = 0, long_min: int = 0) -> None:
         """kad_sync_finish_debug_route: the lane-group width and long_min of the following sync_finish() calls (0:

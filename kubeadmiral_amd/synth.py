@@ -1701,3 +1701,71 @@ def gen_monitor_events(seed: int, n_objects: int = 40, n_clusters: int = 6, roun
                                members=members))
         out.append((now, events))
     return out
+
+
+def gen_revisions(seed: int, O: int, steady: float = 0.85, history: int = 4, env: int = 24, long_every: int = 0):
+    """A synthetic revision-history batch (history.RevisionBatch): ``O`` federated Deployments whose patch is a pod
+    template of ``env`` environment variables (about 60 bytes each; every ``long_every``-th object, if set, has 100
+    times as many) and their listed ControllerRevisions. A share ``steady`` of the objects is in its steady state: one
+    current revision that holds the patch, the highest Revision and every wanted label, and ``history`` old ones
+    within a limit of ``history``, so nothing is to be done. The others are rolling: no current revision (a create),
+    ``history + 2`` old ones (two deletes), a third of them with a current revision numbered too low (a renumber)
+    and one old revision without the object's labels (a relabel). Old revisions hold the patch of an earlier image
+    tag: the same length as the current patch, different in one byte near the end."""
+    from . import gojson, history as H
+
+    rng = np.random.default_rng([seed, 0x726576])
+
+    def template(n_env, tag):
+        return {"metadata": {"labels": {"app": "web", "tier": "frontend"}},
+                "spec": {"containers": [{"name": "main", "image": f"registry.example/web:{tag}",
+                                         "env": [{"name": f"SETTING_{k:04d}", "value": f"value-of-setting-{k:04d}-@@ID@@"} for k in range(n_env)],
+                                         "resources": {"limits": {"cpu": "500m", "memory": "1Gi"}}}],
+                         "terminationGracePeriodSeconds": 30}}
+
+    base = {(long_, tag): gojson.revision_patch(template(env * (100 if long_ else 1), tag)) for long_ in (False, True) for tag in "0123456789"}
+    batch = H.RevisionBatch()
+    plans = []
+    for i in range(O):
+        long_ = bool(long_every) and i % long_every == long_every - 1
+        ident = f"{i:06d}".encode()
+        tags = rng.permutation(10)
+        is_steady = rng.random() < steady
+        n_old = history if is_steady else history + 2
+        plans.append((i, long_, ident, tags, is_steady, n_old, int(rng.integers(0, 3))))
+    # every patch and data string, then their hashes in one vector pass (the listed revisions carry true hash labels)
+    strings, where = [], []
+    for i, long_, ident, tags, is_steady, n_old, kind in plans:
+        for t in tags[:n_old + 1]:  # [0]: the object's own patch, the others its older revisions'
+            strings.append(base[(long_, str(int(t)))].replace(b"@@ID@@", ident))
+    lens = np.array([len(s) for s in strings], np.int64)
+    offs = np.concatenate(([0], np.cumsum(lens)[:-1])).astype(np.int64)
+    blob = np.frombuffer(b"".join(strings), np.uint8)
+    body = H.fnv_numpy(blob, offs, lens)
+    at = 0
+    for i, long_, ident, tags, is_steady, n_old, kind in plans:
+        name, uid = f"web-{i:06d}", f"uid-{i:06d}"
+        wanted = {"uid": uid, "app": "web", "team": f"team-{i % 7}"}
+
+        def label_of(k):  # the hash label NewControllerRevision gave it: FNV over the data, then the collision count "0"
+            h = int(body[at + k])
+            h = ((h * 16777619) & 0xFFFFFFFF) ^ ord("0")
+            return H.hash_label(h)
+
+        def rev(k, number, labels=None, t=0):
+            hl = label_of(k)
+            lab = dict(wanted if labels is None else labels)
+            lab[H.HASH_LABEL] = hl
+            return {"metadata": {"name": H.revision_name(name, hl), "labels": lab, "creationTimestamp": 1700000000 + t},
+                    "revision": number, "data": strings[at + k]}
+
+        revs = [rev(k, k, t=k) for k in range(1, n_old + 1)]
+        if is_steady:
+            revs.append(rev(0, n_old + 1, t=n_old + 1))
+        else:
+            if kind == 0:
+                revs.insert(1, rev(0, 1, t=n_old + 1))  # a current revision numbered too low
+            revs[-1]["metadata"]["labels"] = {"uid": uid, H.HASH_LABEL: revs[-1]["metadata"]["labels"][H.HASH_LABEL]}
+        batch.add(name, wanted, history, 0, strings[at], revs)
+        at += n_old + 1
+    return batch
