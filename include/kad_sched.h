@@ -1711,6 +1711,137 @@ int kad_revision_plan_last_route(kad_ctx* ctx, int32_t* out);
  * [1, 64]) and long_min (0: the route's own) of the following kad_revision_plan calls. */
 int kad_revision_plan_debug_route(kad_ctx* ctx, int32_t force_width, int32_t force_long_min);
 
+/* ------------------------------------------------ sync deletion
+ * The other arm of the sync controller's reconcile (pkg/controllers/sync/controller.go:340-378, 723-979): a federated
+ * object with a deletion timestamp (ensureDeletion → deleteFromClusters or removeManagedLabel), or an event for a
+ * target that has no federated object (reconcile's possibleOrphan arm → removeManagedLabel). Both walk the joined
+ * clusters in handleDeletionInClusters. kad_deletion_plan is that walk before anything is sent; kad_deletion_finish is
+ * what follows the dispatcher's Wait() and, where the delete arm found nothing remaining, ensureRemovedOrUnmanaged's
+ * live checks. The operations, the GETs, DeleteVersions, deleteHistory and the finalizer updates stay with the caller.
+ *
+ * The clusters and the observations are kad_dispatch_plan's: n_clusters (at most KAD_DISPATCH_MAX_CLUSTERS, more is
+ * KAD_EUNSUPPORTED), cluster_flags[C] (KAD_DISPATCH_CL_*; only _READY is read, an unknown bit is KAD_EINVAL),
+ * obj_ob_off[O + 1] / ob_cluster / ob_flags (strictly ascending ids per object, exactly one of KAD_DISPATCH_OB_EXISTS
+ * and _RETRIEVAL_FAILED, _DELETING and _ADOPTED with _EXISTS only).
+ * Per object: obj_flags[O]: KAD_DEL_OBJ_HAS_FINALIZER = the object carries the sync controller's finalizer (:734-739;
+ * without it nothing is walked), _ORPHAN_ALL / _ORPHAN_ADOPTED = GetOrphaningBehavior (never both), _POSSIBLE_ORPHAN =
+ * no federated object exists (:350-363; exclusive with the other three).
+ *
+ * kad_deletion_plan. Per observation, aligned with it: out_op = KAD_DISPATCH_OP_NONE, _DELETE or _REMOVE_LABEL. An
+ * unready cluster is skipped; a failed retrieval is counted and gets no op; in the label-removal arms (orphan all,
+ * possible orphan) an existing object gets _REMOVE_LABEL unless it is _DELETING (:802-807); in the delete arm every
+ * existing object is a remaining cluster and gets _REMOVE_LABEL where _ORPHAN_ADOPTED meets _ADOPTED, else _DELETE, a
+ * _DELETING one included (dispatch/unmanaged.go:93-140 still strips the retain finalizer). Per object: n_ops,
+ * n_remaining (deleteFromClusters' remainingClusters; 0 in the label-removal arms), n_retrieval_failed, obj_pre
+ * (KAD_DEL_PRE_RETRIEVAL_FAILED; _NOT_READY on every object that walks when any joined cluster is not ready), obj_first
+ * (KAD_DEL_ACT_DELETE_HISTORY | _REMOVE_FINALIZER: the orphan-all arm does both before its label removals, :741-766;
+ * _NOTHING: no finalizer, nothing walked, every count 0 and every out_op of the object _NONE).
+ *
+ * kad_deletion_finish takes the same batch and recomputes the plan's decision. results: op_ok[obj_ob_off[O]] (0 or 1;
+ * read only where the plan gives an op), obj_wait[O] (KAD_DEL_WAIT_TIMED_OUT = the operations' Wait() timed out, read
+ * only where the plan gives the object an op, because Wait() over no operation cannot; _CHECK_TIMED_OUT likewise for
+ * the checks, read only where a listed cluster is ready), chk_off[O + 1] / chk_cluster (ascending per object) /
+ * chk_flags (exactly one of KAD_DEL_CHK_*) = the answers of ensureRemovedOrUnmanaged's GETs other than NotFound,
+ * chk_cluster_flags[C] = the joined clusters as listed the second time. A ready cluster without an entry answered
+ * NotFound; an entry on an unready cluster is ignored; an object outside the delete arm, one that failed before the
+ * checks or one with remaining clusters ignores its rows. Outputs per object: obj_status (KAD_DEL_ST_*), obj_reason
+ * (KAD_DEL_RSN_*, the first that holds in the enum's order, which is the reference's: :965-978, :861-866, :867-871,
+ * :908-918), obj_then (KAD_DEL_ACT_DELETE_HISTORY | _REMOVE_FINALIZER where the delete arm verified clean, :877-881 and
+ * :780; _RECORD_ERROR where ensureDeletion records EnsureDeletionFailed, :771-776), n_failed_ops, n_failed_checks (0
+ * where the checks were not reached).
+ *
+ * Everything is validated on the host before any launch (KAD_EINVAL, nothing launched); O == 0 returns 0, launches
+ * nothing and leaves the last route. Neither call touches the resident batch, the last schedule's results or another
+ * stage's timings; a kad_group member accepts both. */
+#define KAD_DEL_OBJ_HAS_FINALIZER 1u
+#define KAD_DEL_OBJ_ORPHAN_ALL 2u
+#define KAD_DEL_OBJ_ORPHAN_ADOPTED 4u
+#define KAD_DEL_OBJ_POSSIBLE_ORPHAN 8u
+#define KAD_DEL_PRE_RETRIEVAL_FAILED 1u
+#define KAD_DEL_PRE_NOT_READY 2u
+#define KAD_DEL_ACT_DELETE_HISTORY 1u
+#define KAD_DEL_ACT_REMOVE_FINALIZER 2u
+#define KAD_DEL_ACT_NOTHING 4u
+#define KAD_DEL_ACT_RECORD_ERROR 8u
+#define KAD_DEL_WAIT_TIMED_OUT 1u
+#define KAD_DEL_WAIT_CHECK_TIMED_OUT 2u
+#define KAD_DEL_CHK_GET_FAILED 1u
+#define KAD_DEL_CHK_DELETING 2u
+#define KAD_DEL_CHK_LABELLED 4u
+#define KAD_DEL_CHK_UNLABELLED 8u
+#define KAD_DEL_ST_OK 0
+#define KAD_DEL_ST_ERROR 1
+#define KAD_DEL_ST_RECHECK 2
+#define KAD_DEL_RSN_NONE 0
+#define KAD_DEL_RSN_TIMED_OUT 1
+#define KAD_DEL_RSN_RETRIEVAL_FAILED 2
+#define KAD_DEL_RSN_NOT_READY 3
+#define KAD_DEL_RSN_OPS_FAILED 4
+#define KAD_DEL_RSN_WAITING 5
+#define KAD_DEL_RSN_CHECK_TIMED_OUT 6
+#define KAD_DEL_RSN_CHECK_NOT_READY 7
+#define KAD_DEL_RSN_CHECKS_FAILED 8
+typedef struct kad_deletion_batch {
+  int32_t n_clusters, n_objects;
+  const uint8_t* cluster_flags; /* [C] KAD_DISPATCH_CL_* */
+  const uint8_t* obj_flags;     /* [O] KAD_DEL_OBJ_* */
+  const int32_t* obj_ob_off;    /* [O + 1] */
+  const int32_t* ob_cluster;    /* [obj_ob_off[O]] */
+  const uint8_t* ob_flags;      /* [obj_ob_off[O]] KAD_DISPATCH_OB_* */
+} kad_deletion_batch;
+typedef struct kad_deletion_view {
+  uint8_t* out_op;             /* [obj_ob_off[O]] KAD_DISPATCH_OP_* */
+  int32_t* n_ops;              /* [O] */
+  int32_t* n_remaining;        /* [O] */
+  int32_t* n_retrieval_failed; /* [O] */
+  uint8_t* obj_pre;            /* [O] KAD_DEL_PRE_* */
+  uint8_t* obj_first;          /* [O] KAD_DEL_ACT_* */
+} kad_deletion_view;
+typedef struct kad_deletion_results {
+  const uint8_t* op_ok;             /* [obj_ob_off[O]] */
+  const uint8_t* obj_wait;          /* [O] KAD_DEL_WAIT_* */
+  const int32_t* chk_off;           /* [O + 1] */
+  const int32_t* chk_cluster;       /* [chk_off[O]] */
+  const uint8_t* chk_flags;         /* [chk_off[O]] KAD_DEL_CHK_* */
+  const uint8_t* chk_cluster_flags; /* [C] KAD_DISPATCH_CL_* */
+} kad_deletion_results;
+typedef struct kad_deletion_finish_view {
+  uint8_t* obj_status;      /* [O] KAD_DEL_ST_* */
+  uint8_t* obj_reason;      /* [O] KAD_DEL_RSN_* */
+  uint8_t* obj_then;        /* [O] KAD_DEL_ACT_* */
+  int32_t* n_failed_ops;    /* [O] */
+  int32_t* n_failed_checks; /* [O] */
+} kad_deletion_finish_view;
+int kad_deletion_plan(kad_ctx* ctx, const kad_deletion_batch* batch, const kad_deletion_view* out);
+int kad_deletion_finish(kad_ctx* ctx, const kad_deletion_batch* batch, const kad_deletion_results* results,
+                        const kad_deletion_finish_view* out);
+/* Host only (no device, no ctx): the same validations; KAD_EUNSUPPORTED above KAD_DISPATCH_MAX_CLUSTERS. */
+int kad_deletion_check(const kad_deletion_batch* batch, const kad_deletion_view* out);
+int kad_deletion_finish_check(const kad_deletion_batch* batch, const kad_deletion_finish_view* out,
+                              const kad_deletion_results* results);
+/* Host only: one (object, observed cluster) pair as both kernels decide it (csrc/kad_deletion.h del_decide): out[0] the
+ * op, out[1] = 1 where the cluster counts as remaining, out[2] = 1 where it counts as a retrieval failure. */
+int kad_deletion_decide(uint32_t obj_flags, int32_t cluster_ready, uint32_t ob_flags, uint8_t out[3]);
+/* ms[0] = inputs to the device, ms[1] = deletion_count_kernel + deletion_kernel, ms[2] = outputs back. */
+int kad_deletion_timing(kad_ctx* ctx, float ms[3]);
+int kad_deletion_finish_timing(kad_ctx* ctx, float ms[3]);
+/* csrc/kad_deletion.h route_deletion: n_long = the objects with more entries (observations; for finish observations
+ * plus check rows) than the route's long_min, short_items = the other objects' entries. out[KAD_DEL_ROUTE_FIELDS] is
+ * [0] the lanes per object (the mean entries of a short object over the entries a lane takes, a power of two in
+ * [1, 64]), [1] long_min, [2] block threads, [3] blocks of the group path, [4] of the long path (four objects a block),
+ * [5] objects between two consecutive objects of one lane group, [6] dynamic LDS bytes a block (the clusters' flags). */
+#define KAD_DEL_ROUTE_FIELDS 7
+int kad_deletion_route_eval(int32_t n_clusters, int32_t n_objects, int32_t n_long, int64_t short_items, int32_t n_cu,
+                            int32_t* out);
+int kad_deletion_finish_route_eval(int32_t n_clusters, int32_t n_objects, int32_t n_long, int64_t short_items,
+                                   int32_t n_cu, int32_t* out);
+int kad_deletion_last_route(kad_ctx* ctx, int32_t* out);
+int kad_deletion_finish_last_route(kad_ctx* ctx, int32_t* out);
+/* Measurement and tests only: the lane-group width (0, or a power of two in [1, 64]) and long_min (0: the route's own)
+ * of the following calls. */
+int kad_deletion_debug_route(kad_ctx* ctx, int32_t force_width, int32_t force_long_min);
+int kad_deletion_finish_debug_route(kad_ctx* ctx, int32_t force_width, int32_t force_long_min);
+
 /* ------------------------------------------------ result application (§8 f3)
  * applySchedulingResult (pkg/controllers/scheduler/scheduler.go:632-695) writes a unit's result into its
  * federated object: the scheduler controller's placement (util.SetPlacementClusterNames,

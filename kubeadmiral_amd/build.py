@@ -17,7 +17,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libkad.so")
-SOURCES = ["kad_kernels.hip", "kad_trigger.hip", "kad_delta.hip", "kad_diff.hip", "kad_explain.hip", "kad_override.hip", "kad_follower.hip", "kad_migrate.hip", "kad_cstat.hip", "kad_statusagg.hip", "kad_rollout.hip", "kad_dispatch.hip", "kad_policyrc.hip", "kad_syncfin.hip", "kad_monitor.hip", "kad_history.hip", "kad_api.hip", "kad_pack.cpp", "kad_objects.cpp"]
+SOURCES = ["kad_kernels.hip", "kad_trigger.hip", "kad_delta.hip", "kad_diff.hip", "kad_explain.hip", "kad_override.hip", "kad_follower.hip", "kad_migrate.hip", "kad_cstat.hip", "kad_statusagg.hip", "kad_rollout.hip", "kad_dispatch.hip", "kad_policyrc.hip", "kad_syncfin.hip", "kad_monitor.hip", "kad_history.hip", "kad_deletion.hip", "kad_api.hip", "kad_pack.cpp", "kad_objects.cpp"]
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h"))  # every header: none can be left out of the stamp
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("KAD_OFFLOAD_ARCH", "gfx950")

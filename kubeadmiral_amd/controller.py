@@ -540,7 +540,7 @@ class BatchReconciler:
         recorded per cluster, whether to recheck after dispatch, ComputePlacementFailed. Its ``selected`` and
         ``rollout_members`` are what :meth:`reconcile_rollout` accepts. :meth:`reconcile_sync_versions` (before the
         operations) and :meth:`reconcile_sync_finish` (after them) are the rest of syncToClusters; objects being
-        deleted (ensureDeletion) and the operations themselves are the caller's."""
+        deleted (ensureDeletion) go to :meth:`reconcile_deletion` and the operations themselves are the caller's."""
         from . import dispatch as DI
 
         if finalizer is None:
@@ -552,6 +552,57 @@ class BatchReconciler:
         if not len(batch):
             return []
         return batch.apply(self.ctx.dispatch_plan(**batch.arrays()))
+
+    # ------------------------------------------------------------------ sync deletion
+    def _deletion_batch(self, objs, clusters, member_objs, finalizer):
+        from . import deletion as DL
+        from . import dispatch as DI
+
+        if finalizer is None:
+            ftc = self.type_config
+            finalizer = DI.cascading_delete_finalizer(ftc.plural_name + ("." + ftc.group if ftc.group else ""))
+        batch = DL.DeletionBatch(self.type_config, clusters, finalizer)
+        for fed, members in zip(objs, member_objs):
+            batch.add(fed, members)
+        return batch
+
+    def reconcile_deletion(self, objs: Sequence[Optional[dict]], clusters: Sequence[dict],
+                           member_objs: Sequence[Dict[str, object]], finalizer: Optional[str] = None) -> list:
+        """The deletion arm of the sync controller's reconcile for a batch (ensureDeletion, deleteFromClusters,
+        removeManagedLabel, handleDeletionInClusters: pkg/controllers/sync/controller.go:340-378, 723-979), before
+        anything is sent: ``objs[i]`` is a federated object with a deletion timestamp (the ones
+        :meth:`reconcile_dispatch`'s callers leave out), or None for a target without a federated object;
+        ``clusters`` and ``member_objs[i]`` as :meth:`reconcile_dispatch` takes them. One kad_deletion_plan answers
+        every object; returns per object a deletion.DeletionPlan: the delete and label-removal operations by cluster,
+        the remaining clusters, the names the error texts list and the actions that come first."""
+        batch = self._deletion_batch(objs, clusters, member_objs, finalizer)
+        if not len(batch):
+            return []
+        return batch.apply_plan(self.ctx.deletion_plan(**batch.arrays()))
+
+    def reconcile_deletion_finish(self, objs: Sequence[Optional[dict]], clusters: Sequence[dict],
+                                  member_objs: Sequence[Dict[str, object]], op_results: Sequence[Dict[str, bool]],
+                                  waits: Optional[Sequence[int]] = None, checks: Optional[Sequence[Dict[str, object]]] = None,
+                                  check_clusters: Optional[Sequence[dict]] = None, finalizer: Optional[str] = None,
+                                  plans: Optional[Sequence] = None) -> list:
+        """What follows the operations of :meth:`reconcile_deletion` on the same batch: ``op_results[i]`` per cluster
+        whether the operation succeeded, ``waits[i]`` the deletion.WAIT_* bits of the two Wait() calls, ``checks[i]``
+        per cluster what ensureRemovedOrUnmanaged's GET answered other than NotFound (the member object, or the
+        exception it failed with) and ``check_clusters`` the joined clusters as listed for the checks (default:
+        unchanged). ``plans``: what :meth:`reconcile_deletion` returned for the same batch (the names the error texts
+        list; default: restated on the host, without a second device call). One kad_deletion_finish decides every
+        object; returns per object a deletion.DeletionOutcome: the worker result, the reason, the reference's error
+        text and the actions that follow. DeleteVersions,
+        deleteHistory, the finalizer's removal and RecordError stay with the caller."""
+        batch = self._deletion_batch(objs, clusters, member_objs, finalizer)
+        if not len(batch):
+            return []
+        if plans is None:
+            from . import deletion as DL
+
+            plans = batch.apply_plan(DL.plan_numpy(**batch.arrays()))
+        res = self.ctx.deletion_finish(**batch.finish_arrays(op_results, waits, checks, check_clusters))
+        return batch.apply_finish(res, plans, check_clusters)
 
     # ------------------------------------------------------------------ sync completion
     def reconcile_sync_versions(self, objs: Sequence[dict], outcomes: Sequence, desired: Sequence[Dict[str, dict]],

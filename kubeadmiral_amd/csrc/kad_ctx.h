@@ -106,7 +106,7 @@ struct Stage {
 };
 enum StageId { STG_DIFF, STG_EXPLAIN, STG_OVERRIDE, STG_FOLLOWER, STG_MIGRATE, STG_TRIGGER, STG_CSTAT, STG_SAGG,
                STG_ROLLOUT, STG_DISPATCH, STG_POLICYRC, STG_SYNCNU, STG_SYNCFIN, STG_MONREC, STG_MONREP, STG_MONIO, STG_REVISION,
-               STG_COUNT };
+               STG_DELPLAN, STG_DELFIN, STG_COUNT };
 
 // The monitor's meters (kad_monitor_*, DESIGN.md §7 "monitor"): the one consumer state that stays on the device
 // between calls. One slot per meter, a column per field; allocated in steps of kad_monitor.h's MON_BTILE slots and

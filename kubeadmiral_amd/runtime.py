@@ -222,6 +222,27 @@ class RevisionView(ctypes.Structure):  # kad_revision_view
                 ("act_rev", ctypes.c_void_p)]
 
 
+class DeletionBatch(ctypes.Structure):  # kad_deletion_batch
+    _fields_ = [("n_clusters", ctypes.c_int32), ("n_objects", ctypes.c_int32), ("cluster_flags", ctypes.c_void_p),
+                ("obj_flags", ctypes.c_void_p), ("obj_ob_off", ctypes.c_void_p), ("ob_cluster", ctypes.c_void_p),
+                ("ob_flags", ctypes.c_void_p)]
+
+
+class DeletionView(ctypes.Structure):  # kad_deletion_view
+    _fields_ = [("out_op", ctypes.c_void_p), ("n_ops", ctypes.c_void_p), ("n_remaining", ctypes.c_void_p),
+                ("n_retrieval_failed", ctypes.c_void_p), ("obj_pre", ctypes.c_void_p), ("obj_first", ctypes.c_void_p)]
+
+
+class DeletionResults(ctypes.Structure):  # kad_deletion_results
+    _fields_ = [("op_ok", ctypes.c_void_p), ("obj_wait", ctypes.c_void_p), ("chk_off", ctypes.c_void_p),
+                ("chk_cluster", ctypes.c_void_p), ("chk_flags", ctypes.c_void_p), ("chk_cluster_flags", ctypes.c_void_p)]
+
+
+class DeletionFinishView(ctypes.Structure):  # kad_deletion_finish_view
+    _fields_ = [("obj_status", ctypes.c_void_p), ("obj_reason", ctypes.c_void_p), ("obj_then", ctypes.c_void_p),
+                ("n_failed_ops", ctypes.c_void_p), ("n_failed_checks", ctypes.c_void_p)]
+
+
 class MonitorReportBatch(ctypes.Structure):  # kad_monitor_report_batch
     _fields_ = [("now_ns", ctypes.c_int64), ("n_types", ctypes.c_int32), ("timer_cap", ctypes.c_int32)]
 
@@ -298,6 +319,9 @@ _CONSUMER_ABI = {
     "monitor_reconcile": ("kad_monitor_reconcile", (), (_I32, _I32, _I64, _I32), (_I32, _I32)),
     "monitor_report": ("kad_monitor_report", (), (_I64, _I32, _I32), (_I32, _I32)),
     "revision_plan": ("kad_revision_plan", (), (_I32, _I32, _I32, _I64, _I64, _I64, _I32), (_I32, _I32)),
+    "deletion": ("kad_deletion_plan", (), (_I32, _I32, _I32, _I64, _I32), (_I32, _I32)),
+    # (kad_deletion_finish itself takes the results between the batch and the view: bound below the loop)
+    "deletion_finish": ("kad_deletion_finish", (ctypes.c_void_p,), (_I32, _I32, _I32, _I64, _I32), (_I32, _I32)),
 }
 
 
@@ -365,6 +389,9 @@ def load_library(path: str = LIB_PATH):
         L.kad_monitor_info.argtypes = [P, P]
     if hasattr(L, "kad_dispatch_decide"):
         L.kad_dispatch_decide.argtypes = [ctypes.c_uint32, ctypes.c_int32, ctypes.c_uint32, ctypes.c_uint32, P]
+    if hasattr(L, "kad_deletion_finish"):  # (absent from libraries of older revisions: A/B runs)
+        L.kad_deletion_finish.argtypes = [P, P, P, P]
+        L.kad_deletion_decide.argtypes = [ctypes.c_uint32, ctypes.c_int32, ctypes.c_uint32, P]
     L.kad_debug_inject_fault.argtypes = [P, I]
     L.kad_debug_plan_force_workspace.argtypes = [P, I]
     L.kad_trigger_suffix_upload.argtypes = [P, P, SZ]
@@ -701,6 +728,94 @@ def dispatch_args(fill: int = 0, **arrays):
 def dispatch_check(**arrays) -> int:
     """kad_dispatch_check: kad_dispatch_plan's validation of :func:`dispatch_args` arguments; no GPU."""
     return _check("dispatch", dispatch_args(**arrays))
+
+
+DELETION_ROUTE = ("width", "long_min", "threads", "grid", "long_grid", "stride", "lds")  # both calls' record
+
+
+def deletion_route_eval(n_clusters: int, n_objects: int, n_long: int, short_items: int, n_cu: int = 256) -> dict:
+    """kad_deletion_route_eval: the launch decision of a deletion_plan (needs no GPU)."""
+    return _route_eval("deletion", DELETION_ROUTE, n_clusters, n_objects, n_long, short_items, n_cu, error=KadError)
+
+
+def deletion_finish_route_eval(n_clusters: int, n_objects: int, n_long: int, short_items: int, n_cu: int = 256) -> dict:
+    """kad_deletion_finish_route_eval: the launch decision of a deletion_finish (needs no GPU)."""
+    return _route_eval("deletion_finish", DELETION_ROUTE, n_clusters, n_objects, n_long, short_items, n_cu, error=KadError)
+
+
+def deletion_decide(obj_flags: int, cluster_ready: bool, ob_flags: int = 0):
+    """kad_deletion_decide: (op, remaining, retrieval_failed) of one (object, observed cluster) pair as both kernels
+    decide it (no GPU)."""
+    out = (ctypes.c_uint8 * 3)()
+    rc = load_library().kad_deletion_decide(obj_flags, 1 if cluster_ready else 0, ob_flags, out)
+    if rc != 0:
+        raise KadError(rc, "kad_deletion_decide")
+    return int(out[0]), bool(out[1]), bool(out[2])
+
+
+_DELETION_IN = (("cluster_flags", np.uint8), ("obj_flags", np.uint8), ("obj_ob_off", np.int32), ("ob_cluster", np.int32),
+                ("ob_flags", np.uint8))
+_DELETION_OUT = (("out_op", np.uint8, 1), ("n_ops", np.int32, 0), ("n_remaining", np.int32, 0),
+                 ("n_retrieval_failed", np.int32, 0), ("obj_pre", np.uint8, 0), ("obj_first", np.uint8, 0))
+_DELETION_RES = (("op_ok", np.uint8), ("obj_wait", np.uint8), ("chk_off", np.int32), ("chk_cluster", np.int32),
+                 ("chk_flags", np.uint8), ("chk_cluster_flags", np.uint8))
+_DELETION_FIN_OUT = (("obj_status", np.uint8, 0), ("obj_reason", np.uint8, 0), ("obj_then", np.uint8, 0),
+                     ("n_failed_ops", np.int32, 0), ("n_failed_checks", np.int32, 0))
+
+
+def _deletion_counts(a: dict, arrays: dict):
+    C = int(arrays.get("n_clusters", len(a["cluster_flags"]) if "cluster_flags" in a else 0))
+    O = len(a["obj_flags"]) if "obj_flags" in a else 0
+    oo = a.get("obj_ob_off")
+    B = int(oo[-1]) if oo is not None and len(oo) == O + 1 and 0 <= int(oo[-1]) < 2 ** 31 else 0
+    return C, O, B
+
+
+def _filled(out: dict, fill: int) -> dict:
+    if fill:
+        for o in out.values():
+            o.view(np.uint8)[:] = fill
+    return out
+
+
+def deletion_args(fill: int = 0, pad: int = 0, **arrays):
+    """The kad_deletion_batch / kad_deletion_view of one call with the arrays that back them (the batch's fields by
+    name; the counts are taken from cluster_flags and obj_flags as they are, so that a malformed batch reaches the
+    library's validation; ``n_clusters`` overrides the first). Every output has ``pad`` more elements than the call
+    writes and every byte of it starts as ``fill``. Returns (batch, view, the input arrays, the output arrays by
+    name)."""
+    a = _flat(_DELETION_IN, arrays)
+    C, O, B = _deletion_counts(a, arrays)
+    b, v, a, out = _call_args(DeletionBatch, DeletionView, (C, O), _DELETION_IN, _DELETION_OUT, a, {0: O + pad, 1: B + pad})
+    return b, v, a, _filled(out, fill)
+
+
+def deletion_finish_args(fill: int = 0, pad: int = 0, **arrays):
+    """The kad_deletion_batch / kad_deletion_finish_view / kad_deletion_results of one kad_deletion_finish, as
+    :func:`deletion_args` builds the plan's. Returns (batch, view, the arrays kept alive, the output arrays by name,
+    results)."""
+    a = _flat(_DELETION_IN, arrays)
+    r = _flat(_DELETION_RES, arrays)
+    C, O, B = _deletion_counts(a, arrays)
+    # the library gets pointers only: an array it reads by the batch's counts must have that many elements (an empty
+    # one is passed as missing and rejected by the validation)
+    for k, n in (("chk_cluster_flags", len(a["cluster_flags"]) if "cluster_flags" in a else 0), ("op_ok", B), ("obj_wait", O)):
+        if k in r and len(r[k]) not in (0, n):
+            raise ValueError(f"{k} has {len(r[k])} elements, the batch's counts say {n}")
+    b, v, a, out = _call_args(DeletionBatch, DeletionFinishView, (C, O), _DELETION_IN, _DELETION_FIN_OUT, a, {0: O + pad})
+    res = DeletionResults(*(r[k].ctypes.data if k in r and len(r[k]) else None for k, _ in _DELETION_RES))
+    return b, v, (a, r), _filled(out, fill), res
+
+
+def deletion_check(**arrays) -> int:
+    """kad_deletion_check: kad_deletion_plan's validation of :func:`deletion_args` arguments; no GPU."""
+    return _check("deletion", deletion_args(**arrays))
+
+
+def deletion_finish_check(**arrays) -> int:
+    """kad_deletion_finish_check: kad_deletion_finish's validation of :func:`deletion_finish_args` arguments; no GPU."""
+    args = deletion_finish_args(**arrays)
+    return _check("deletion_finish", args, ctypes.byref(args[4]))
 
 
 POLICYRC_ROUTE = ("path", "bins", "threads", "grid", "vec", "apply_grid")
@@ -1281,6 +1396,45 @@ class Context:
     def dispatch_last_route(self) -> dict:
         """kad_dispatch_last_route: what the last dispatch_plan() launched (dispatch_route_eval's record)."""
         return self._last_route("dispatch", DISPATCH_ROUTE)
+
+    def deletion_plan(self, fill: int = 0, pad: int = 0, **arrays) -> dict:
+        """kad_deletion_plan → {out_op (aligned with the observations), n_ops[O], n_remaining[O],
+        n_retrieval_failed[O], obj_pre[O], obj_first[O]}. Arguments as :func:`deletion_args`
+        (deletion.DeletionBatch.arrays())."""
+        return self._consume("kad_deletion_plan", deletion_args(fill, pad, **arrays))
+
+    def deletion_finish(self, fill: int = 0, pad: int = 0, **arrays) -> dict:
+        """kad_deletion_finish → {obj_status[O], obj_reason[O], obj_then[O], n_failed_ops[O], n_failed_checks[O]}.
+        Arguments as :func:`deletion_finish_args` (deletion.DeletionBatch.finish_arrays())."""
+        b, v, _keepalive, out, res = deletion_finish_args(fill, pad, **arrays)
+        self._chk(self.L.kad_deletion_finish(self.h, ctypes.byref(b), ctypes.byref(res), ctypes.byref(v)))
+        return out
+
+    def deletion_timing(self):
+        """kad_deletion_timing: ms of the last deletion_plan() — (inputs to the device, deletion_count_kernel +
+        deletion_kernel, outputs back)."""
+        return self._timing("deletion", 3)
+
+    def deletion_finish_timing(self):
+        """kad_deletion_finish_timing: ms of the last deletion_finish(), as :meth:`deletion_timing`."""
+        return self._timing("deletion_finish", 3)
+
+    def deletion_last_route(self) -> dict:
+        """kad_deletion_last_route: what the last deletion_plan() launched (deletion_route_eval's record)."""
+        return self._last_route("deletion", DELETION_ROUTE)
+
+    def deletion_finish_last_route(self) -> dict:
+        """kad_deletion_finish_last_route: what the last deletion_finish() launched."""
+        return self._last_route("deletion_finish", DELETION_ROUTE)
+
+    def deletion_debug_route(self, width: int = 0, long_min: int = 0) -> None:
+        """kad_deletion_debug_route: the lane-group width and long_min of the following deletion_plan() calls (0:
+        the route's own). Measurement and tests only."""
+        self._debug_route("deletion", width, long_min)
+
+    def deletion_finish_debug_route(self, width: int = 0, long_min: int = 0) -> None:
+        """kad_deletion_finish_debug_route: as :meth:`deletion_debug_route`, for deletion_finish()."""
+        self._debug_route("deletion_finish", width, long_min)
 
     def policyrc_count(self, **arrays) -> dict:
         """kad_policyrc_count → {new_count[P], new_total[P], state[P] (PRC_FLAGGED | PRC_UPDATE | PRC_NEGATIVE),

@@ -1587,6 +1587,46 @@ def gen_dispatch(seed: int, W: int, C: int, placed: int = 5, observed: float = 0
                 out_off=pl_off + ob_off)
 
 
+def gen_deletion(seed: int, W: int, C: int, observed: int = 10, healthy: float = 1.0, adopted: float = 0.1):
+    """A synthetic sync-deletion batch as kad_deletion_finish's arrays (the keyword arguments of
+    Context.deletion_finish; those of Context.deletion_plan are ``DELETION_PLAN_KEYS`` of them): ``W`` terminating
+    objects over ``C`` joined clusters, each held by ``observed`` - 2 .. ``observed`` + 2 clusters (uniform), except
+    that one object in five is on its second pass and held by none. 2 % of the lookups failed, 20 % of the member
+    objects are already being deleted, a share ``adopted`` was adopted. A share ``healthy`` of the clusters is ready,
+    at both listings independently. 85 % of the objects carry the finalizer and delete, 5 % orphan all, 5 % orphan the
+    adopted, 3 % have no federated object, 2 % no finalizer. 1 % of the operations fail, 0.5 % of the objects time
+    out in either Wait(); every object has check rows on 0 to 2 clusters (an answer each, uniform)."""
+    rng = np.random.default_rng([seed, 0x64656C])
+    cluster_flags = np.where(rng.random(C) < healthy, 1 | 8, rng.integers(0, 8, C) * 2).astype(np.uint8)
+    chk_cluster_flags = np.where(rng.random(C) < healthy, 1 | 8, rng.integers(0, 8, C) * 2).astype(np.uint8)
+    u = rng.random(W)
+    obj_flags = np.select([u < 0.85, u < 0.90, u < 0.95, u < 0.98], [1, 1 | 2, 1 | 4, 8], 0).astype(np.uint8)
+
+    def rows(n_per):
+        off = np.zeros(W + 1, np.int64)
+        off[1:] = np.cumsum(n_per)
+        owner = np.repeat(np.arange(W), n_per)
+        keys = np.unique(owner * C + rng.integers(0, C, len(owner)))  # (a duplicate draw: one entry fewer)
+        off[1:] = np.cumsum(np.bincount(keys // C, minlength=W))
+        return off, keys % C
+
+    n_ob = np.where(rng.random(W) < 0.2, 0, rng.integers(max(observed - 2, 0), observed + 3, W))
+    ob_off, ob_cluster = rows(np.minimum(n_ob, C))
+    B = len(ob_cluster)
+    u = rng.random(B)
+    ob_flags = np.where(u < 0.02, 8, np.where(u < 0.22, 1 | 2, 1) | np.where(rng.random(B) < adopted, 4, 0)).astype(np.uint8)
+    chk_off, chk_cluster = rows(np.minimum(rng.integers(0, 3, W), C))
+    K = len(chk_cluster)
+    return dict(cluster_flags=cluster_flags, obj_flags=obj_flags, obj_ob_off=ob_off.astype(np.int32),
+                ob_cluster=ob_cluster.astype(np.int32), ob_flags=ob_flags, op_ok=(rng.random(B) >= 0.01).astype(np.uint8),
+                obj_wait=((rng.random(W) < 0.005) * 1 + (rng.random(W) < 0.005) * 2).astype(np.uint8),
+                chk_off=chk_off.astype(np.int32), chk_cluster=chk_cluster.astype(np.int32),
+                chk_flags=(1 << rng.integers(0, 4, K)).astype(np.uint8), chk_cluster_flags=chk_cluster_flags)
+
+
+DELETION_PLAN_KEYS = ("cluster_flags", "obj_flags", "obj_ob_off", "ob_cluster", "ob_flags")
+
+
 def gen_sync_finish(seed: int, W: int, C: int, touched: int, steady: float = 0.8):
     """A synthetic sync-completion batch as kad_sync_finish's arrays (the arguments of Context.sync_finish, the four
     scalars included): ``W`` federated objects over ``C`` joined clusters, each with ``touched`` dispatcher records
